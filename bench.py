@@ -1,6 +1,11 @@
 """Headline benchmark: SSB SF100 flattened lineorder, Q1.1-Q1.3 (scan filter + SUM), per GPU.
 
-Contract (driver): `python bench.py --gpus N --steps K --warmup W`; N>1 is launched by
+Contract (driver): `python bench.py --gpus N --steps K --warmup W` is the plain run: it loads the headline (sorted)
+layout, warms up, times exactly K steps and prints the result line (metric / value / unit / higher_is_better / dtype /
+ms_per_step = the milliseconds one timed step took), nothing else. `--dump-outputs DIR` also writes what the last
+timed step returned (dump_outputs). Everything else described below -- the unsorted layout, the roofline pass, the
+concurrent clients, the parity checks against the CPU, the CPU baselines, the group-by legs (c3, c5), the config legs
+(c1, c4) and the merged C5 -- runs only with `--full`, after the same timed steps. N>1 is launched by
 torch.distributed.run with one rank per GPU, or, without it, by this script itself (spawn_ranks: N rank processes
 started before any GPU call, rank 0's line printed). A step = Q1.1 + Q1.2 + Q1.3, each one query over 100 segments
 x 6M rows per GPU (SF100 per GPU, weak scaling). At N = 1 the rank holds exactly those 100 (BASELINE C2); at
@@ -111,7 +116,9 @@ def run_c5(args, dist, qc, gsegs, torch):
 
 
 def run_layout(args, dist, queries, qcs, gsegs, torch):
-    """Warm-up, then exactly args.steps timed steps bracketed by barrier + synchronize on both sides."""
+    """Warm-up, then exactly args.steps timed steps bracketed by barrier + synchronize on both sides. Returns the
+    blocks of the last timed step too (`last`: what --dump-outputs writes); the passes after the timed region (parity
+    answers, roofline kernel durations, concurrent clients) run only with --full."""
     from pinot_amd.engine.distributed import distributed_block
     from pinot_amd.engine.plan import GpuInstancePlanMaker
     pm = GpuInstancePlanMaker()
@@ -134,6 +141,7 @@ def run_layout(args, dist, queries, qcs, gsegs, torch):
                 run_query(q)
         lat = {q: [] for q in queries}
         kstats = {q: [] for q in queries}
+        last = {}
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
@@ -145,6 +153,7 @@ def run_layout(args, dist, queries, qcs, gsegs, torch):
                 lat[q].append((time.perf_counter() - ts) * 1e3)
                 kstats[q].append((blk.filter_kernel_ms, blk.agg_kernel_ms, blk.filter_bytes, blk.agg_bytes,
                                    bool(getattr(blk, "fused", False)), int(getattr(blk, "stream_bytes", 0) or 0)))
+                last[q] = blk
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -158,6 +167,10 @@ def run_layout(args, dist, queries, qcs, gsegs, torch):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if not args.full:
+        for op in ops.values():
+            op.close()
+        return elapsed, lat, kstats, None, None, None, last
     # one more execution per query, outside the timed region: this rank's answers, checked against the CPU
     # restatement on the same segments (check_parity)
     answers = {q: ops[q].next_block() for q in queries}
@@ -205,7 +218,39 @@ def run_layout(args, dist, queries, qcs, gsegs, torch):
             concurrent = time.perf_counter() - t0
     for op in ops.values():
         op.close()
-    return elapsed, lat, kstats, answers, concurrent, kstats_ext
+    return elapsed, lat, kstats, answers, concurrent, kstats_ext, last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _as_floats(v):
+    """One intermediate result as float64s: a number, a tuple of numbers (AVG, MINMAXRANGE) or an array (HLL
+    registers). The SUMs of the headline are integers below 2^53 (check_parity), exact in float64."""
+    return np.atleast_1d(np.asarray(v, dtype=np.float64)).ravel()
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the last timed step returned to its caller, one float64 .npy per query and part:
+    <query>.results.npy (an aggregation block's intermediates in SELECT order; a group-by block's, group after group
+    in the order of the sorted key tuples, <query>.num_groups.npy beside it) and <query>.num_docs_scanned.npy. The
+    inputs are generated from --seed, so two builds run with the same arguments write comparable files. An output
+    above the 64 MB budget is cut to its first values (the same ones in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // 8
+    for q, blk in last.items():
+        arrays = {"num_docs_scanned": _as_floats(blk.stats.num_docs_scanned)}
+        if hasattr(blk, "results"):
+            vals = [_as_floats(v) for v in blk.results]
+        else:
+            groups = blk.groups
+            vals = [_as_floats(v) for k in sorted(groups, key=str) for v in groups[k]]
+            arrays["num_groups"] = _as_floats(len(groups))
+        arrays["results"] = np.concatenate(vals) if vals else np.zeros(0, dtype=np.float64)
+        for name, a in arrays.items():
+            a = a[:max(budget, 0)]
+            budget -= a.size
+            np.save(os.path.join(out_dir, f"{q}.{name}.npy"), a)
 
 
 def check_parity(queries, qcs, answers, raws, dist, torch):
@@ -675,7 +720,19 @@ def main():
     ap.add_argument("--touched-json", default=latest_profile("touched"),
                     help="64-B lines the gathers touch per query and layout (tools/touched_lines.py)")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline: the unsorted layout, the "
+                         "roofline pass, the concurrent clients, the parity checks, the CPU baselines, the group-by "
+                         "and config legs and the merged C5 (default: the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step of the headline layout returned as DIR/<query>.<part>.npy "
+                         "(float64; rank 0's blocks, which at N > 1 are the merged ones)")
     args = ap.parse_args()
+    if not args.full:  # the plain run: the headline layout's timed steps alone
+        args.layout = "sorted" if args.layout == "both" else args.layout
+        args.group_by = args.configs = ""
+        args.c5 = "off"
+        args.no_cpu_baseline = args.no_parity = args.no_concurrent = True
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus or 1) > 1:
@@ -744,12 +801,16 @@ def main():
         head = gsegs[:head_segs]
         raws = all_raws[:head_segs]
         rows_per_rank = sum(s.num_docs for s in head)
-        elapsed, lat, kstats, answers, concurrent, kstats_ext = run_layout(args, dist, queries, qcs, head, torch)
-        rf = roofline(kstats_ext, queries, traffic, touched, layout, args.steps)
-        rf["timing"] = ("kernel durations from HIP events recorded by each launch's dispatch packet (PHIP_EXT_EVENTS=1, "
-                        "the timed steps' executions repeated outside the timed region, whose own steps ran without "
-                        "timing markers)")
-        rb = roofline(kstats, queries, traffic, touched, layout, args.steps) if args.timed_markers else None
+        elapsed, lat, kstats, answers, concurrent, kstats_ext, last = run_layout(args, dist, queries, qcs, head, torch)
+        if li == 0 and rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
+        rf = None
+        if args.full:
+            rf = roofline(kstats_ext, queries, traffic, touched, layout, args.steps)
+            rf["timing"] = ("kernel durations from HIP events recorded by each launch's dispatch packet "
+                            "(PHIP_EXT_EVENTS=1, the timed steps' executions repeated outside the timed region, whose "
+                            "own steps ran without timing markers)")
+        rb = roofline(kstats, queries, traffic, touched, layout, args.steps) if rf and args.timed_markers else None
         if rb and rb["kernel"]:
             rf["bracket_events"] = {"kernel": rb["kernel"], "frac": rb["frac"],
                                     "ms_per_launch": rb["kernels"][rb["kernel"]]["ms_per_launch"],
@@ -839,9 +900,10 @@ def main():
                                    f"{'RCCL' if args.dist_backend == 'nccl' else args.dist_backend}") if world > 1
                    else "one GPU (no collective)"},
         "p50_latency_ms": {q: round(float(np.median(head["lat"][q])), 3) for q in queries},
-        "roofline": head["roofline"],
         "load_s": round(head["load_s"], 1),
     }
+    if args.full:
+        out["roofline"] = head["roofline"]
     if "cpu" in head:
         out["cpu_baseline"] = head["cpu"]
     if "concurrent" in head:

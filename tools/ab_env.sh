@@ -1,19 +1,20 @@
 #!/bin/bash
-# A/B of library settings inside one GPU call (boxes differ by ~8 %): runs bench.py once per "NAME=VALUE ..."
-# argument set, recording the JSON lines. usage: tools/ab_env.sh <tag> "PHIP_FUSE=0" "PHIP_FUSE=1" ...
+# A/B of library settings inside one GPU call (boxes differ by ~8 %): runs bench.py --full once per "NAME=VALUE ..."
+# argument set (both layouts and the per-kernel roofline are read below), recording the JSON lines under $OUT
+# (default bench_out/). usage: tools/ab_env.sh <tag> "PHIP_FUSE=0" "PHIP_FUSE=1" ...
 set -u
 TAG=$1; shift
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 for cfg in "$@"; do
-  echo "== $cfg" >> gpurun_out/ab_$TAG.log
-  env $cfg timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 10 --warmup 3 ${BENCH_ARGS:-} > gpurun_out/ab_tmp.log 2>&1 || { tail -20 gpurun_out/ab_tmp.log; exit 1; }
-  tail -1 gpurun_out/ab_tmp.log >> gpurun_out/ab_$TAG.log
+  echo "== $cfg" >> "$OUT/ab_$TAG.log"
+  env $cfg timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 10 --warmup 3 ${BENCH_ARGS:-} > "$OUT/ab_tmp.log" 2>&1 || { tail -20 "$OUT/ab_tmp.log"; exit 1; }
+  tail -1 "$OUT/ab_tmp.log" >> "$OUT/ab_$TAG.log"
 done
-python3 - "$TAG" <<'PY'
+python3 - "$OUT/ab_$TAG.log" <<'PY'
 import json, sys
-tag = sys.argv[1]
 cfg = None
-for line in open(f"gpurun_out/ab_{tag}.log"):
+for line in open(sys.argv[1]):
     if line.startswith("== "):
         cfg = line[3:].strip(); continue
     try:

@@ -18,7 +18,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   step pytest_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 150 --timeout-method thread
   step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
-step bench 600 python -u bench.py --steps 10 --warmup 3 "$@"
+step bench 600 python -u bench.py --full --steps 10 --warmup 3 "$@"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 B="--no-cpu-baseline --steps 10 --warmup 3 $*"
 # one kernel-trace summary per layout, so the headline (sorted) kernels' averages read straight from their own file
