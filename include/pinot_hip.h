@@ -159,6 +159,36 @@ typedef struct phip_filter_node {
 #define PHIP_AGG_MIN 2   /* MinAggregationFunction (default +inf) */
 #define PHIP_AGG_MAX 3   /* MaxAggregationFunction (default -inf) */
 #define PHIP_AGG_HLL 4   /* DistinctCountHLLAggregationFunction: HyperLogLog(log2m) registers */
+#define PHIP_AGG_DISTINCT 5 /* DistinctCountAggregationFunction: exact, dictionary-id bitmap */
+/* PHIP_AGG_DISTINCT (DistinctCountAggregationFunction over BaseDistinctAggregateAggregationFunction,
+ * pinot-core/.../query/aggregation/function/BaseDistinctAggregateAggregationFunction.java:131-160 aggregates a
+ * dictionary column as a bitmap of dictionary ids, :306-330 its group-by form, :671-690 converts ids to a value set
+ * when the segment result is extracted, :760-800 merges by set union). Here the ids are the QUERY-GLOBAL dictionary's
+ * (the sorted union of the segments' dictionaries), so one device bitmap is already the merged intermediate of every
+ * segment of the query. expr must be PHIP_EXPR_COLUMN and column_a a dictionary-encoded column (INT / LONG / FLOAT /
+ * DOUBLE / STRING) in every segment. Each PHIP_AGG_DISTINCT aggregation is one "distinct slot", numbered in
+ * aggregation order. Results: values[] / long_values[] hold the exact count (long_exact = 1) and
+ * phip_result.distinct_words the bitmaps:
+ *   row of group g = distinct_words + g * distinct_word_offsets[num_distinct];
+ *   slot s of it   = row + distinct_word_offsets[s], ceil(card_s / 32) u32 words, card_s = the cardinality that
+ *                    phip_result_distinct_dictionary(result, s) returns; bit i of word w = global id 32 w + i is
+ *                    present; bits at and beyond card_s are 0.
+ * The words over the returned dictionary are the mergeable intermediate: the union of two results equals the OR of
+ * their words once both are re-based on the union of their dictionaries' values (within one result every group and
+ * every segment already shares the dictionary, so there the union IS the OR).
+ * PHIP_ERR_UNSUPPORTED (the CPU plan maker answers) for: a raw (no-dictionary) argument column; an expression
+ * argument; several filter programs (FILTER(WHERE) / CASE) or null_group_by beside a DISTINCT; hash-table, tuple
+ * (> 2^62) and raw-key group-by key spaces; bitmaps above PHIP_DISTINCT_MAX_BYTES (environment, default 256 MiB:
+ * dense key space x sum over slots of ceil(card_s / 32) x 4 bytes); an ORDER BY term or order_by_aggregation on a
+ * DISTINCT aggregation unless the dense key space is at most trim_size (the server trim can then never fire, and
+ * ordering is the broker reduce's job as for every untrimmed result); node plans (segments on several devices or
+ * PHIP_NODE_SPLIT) and phip_plan_execute_partial; a library built without the distinct pass. phip_plan_execute (not
+ * plan creation) returns PHIP_ERR_UNSUPPORTED when the groups of a plan over SEVERAL segments reach num_groups_limit:
+ * the limit is per segment (a segment that dropped a key skips that key's docs), while a bitmap row holds a key's
+ * values over every segment; over one segment the kept groups' sets are exact and are returned.
+ * PHIP_DISTINCT_LDS_WORDS (environment, read at plan creation, default 8192): without a group-by, bitmaps of at most
+ * this many words in all are combined per workgroup in LDS and flushed with one global atomic OR per non-zero word;
+ * larger ones, and every group-by, set bits in the global bitmap directly (test before set). */
 
 #define PHIP_EXPR_COLUMN 0 /* a */
 #define PHIP_EXPR_ADD 1    /* a + b   (AdditionTransformFunction) */
@@ -318,6 +348,17 @@ typedef struct phip_result {
    * all segments -- the reference's numDocsScanned when programs are the plan maker's own device (the null-handling
    * group-by's IS NOT NULL programs), not FilteredGroupByOperator infos. For a phip_plan_finish result: this GPU's. */
   const int64_t *program_docs_matched;
+  /* PHIP_AGG_DISTINCT (see its definition above): the number of distinct slots, the groups' bitmap rows back to back
+   * (num_groups x distinct_word_offsets[num_distinct] words) and the num_distinct + 1 word offsets of the slots
+   * inside a row. NULL / 0 without a DISTINCT aggregation. */
+  int32_t num_distinct;
+  int32_t reserved_distinct;
+  const uint32_t *distinct_words;
+  const int64_t *distinct_word_offsets;
+  /* Device time of the distinct pass (bitmap clear + mark kernel; the finish kernel is not in it). A measurement
+   * aid like the other *_kernel_ms fields: it reads 0 when the execution recorded no timing markers
+   * (PHIP_KERNEL_TIMING=0 on an aggregation-only plan) and when the plan replayed its captured graph (PHIP_GRAPH). */
+  double distinct_kernel_ms;
 } phip_result;
 
 typedef struct phip_dictionary_view {
@@ -365,6 +406,12 @@ PHIP_API int32_t phip_plan_cancel(uint64_t plan);
 PHIP_API int32_t phip_result_dictionary(const phip_result *result, int32_t group_by_index,
                                         phip_dictionary_view *out_view);
 PHIP_API void phip_result_free(phip_result *result);
+
+/* The query-global dictionary of distinct slot `distinct_index` (the ids phip_result.distinct_words' bits stand for):
+ * the sorted union of the column's dictionary values over the query's segments, exactly as phip_result_dictionary
+ * returns a group-by column's. */
+PHIP_API int32_t phip_result_distinct_dictionary(const phip_result *result, int32_t distinct_index,
+                                                 phip_dictionary_view *out_view);
 
 /* Values of select column k of a selection result that holds STRING dictionary ids. */
 PHIP_API int32_t phip_result_select_dictionary(const phip_result *result, int32_t select_index,

@@ -31,7 +31,7 @@ class RawRange(ctypes.Structure):
                 ("hi_real", ctypes.c_double), ("lo_inclusive", ctypes.c_int32), ("hi_inclusive", ctypes.c_int32)]
 
 
-AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_HLL = range(5)
+AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_HLL, AGG_DISTINCT = range(6)
 EXPR_COLUMN, EXPR_ADD, EXPR_SUB, EXPR_MUL = range(4)
 
 EXPORTED_SYMBOLS = (
@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "phip_result_dictionary", "phip_result_free", "phip_filter_bitmap", "phip_plan_create", "phip_plan_execute",
     "phip_plan_destroy", "phip_global_dictionary", "phip_plan_execute_partial", "phip_plan_finish",
     "phip_runtime_versions", "phip_plan_abandon_partial", "phip_result_select_dictionary",
-    "phip_plan_set_deadline", "phip_plan_cancel", "phip_plan_exchange",
+    "phip_plan_set_deadline", "phip_plan_cancel", "phip_plan_exchange", "phip_result_distinct_dictionary",
 )
 
 # phip_plan_exchange kinds (include/pinot_hip.h "node plans")
@@ -125,12 +125,15 @@ class Result(ctypes.Structure):
                 ("num_rows", ctypes.c_int64), ("num_select", ctypes.c_int32), ("reserved_select", ctypes.c_int32),
                 ("select_types", ctypes.POINTER(ctypes.c_int32)), ("select_values", ctypes.POINTER(ctypes.c_uint64)),
                 ("segment_docs_matched", ctypes.POINTER(ctypes.c_int64)), ("stream_bytes", ctypes.c_int64),
-                ("program_docs_matched", ctypes.POINTER(ctypes.c_int64))]
+                ("program_docs_matched", ctypes.POINTER(ctypes.c_int64)),
+                ("num_distinct", ctypes.c_int32), ("reserved_distinct", ctypes.c_int32),
+                ("distinct_words", ctypes.POINTER(ctypes.c_uint32)),
+                ("distinct_word_offsets", ctypes.POINTER(ctypes.c_int64)), ("distinct_kernel_ms", ctypes.c_double)]
 
 
 # phip_result's scalar image in one read (the aggregation-only fast path of plan._block_from_result): the fields in
 # declaration order, natural alignment (checked against ctypes below)
-RESULT_IMAGE = struct.Struct("<4q4iq2i4Q2d2iQ2d3q2i3QqQ")
+RESULT_IMAGE = struct.Struct("<4q4iq2i4Q2d2iQ2d3q2i3QqQ2i2Qd")
 assert RESULT_IMAGE.size == ctypes.sizeof(Result)
 
 
@@ -231,6 +234,8 @@ def load(with_torch: bool = False):
     lib.phip_result_dictionary.restype = i32
     lib.phip_result_select_dictionary.argtypes = [ctypes.POINTER(Result), i32, ctypes.POINTER(DictionaryView)]
     lib.phip_result_select_dictionary.restype = i32
+    lib.phip_result_distinct_dictionary.argtypes = [ctypes.POINTER(Result), i32, ctypes.POINTER(DictionaryView)]
+    lib.phip_result_distinct_dictionary.restype = i32
     lib.phip_result_free.argtypes = [ctypes.POINTER(Result)]
     lib.phip_result_free.restype = None
     lib.phip_filter_bitmap.argtypes = [ctypes.POINTER(QueryDesc), ctypes.POINTER(u64), i64]

@@ -74,6 +74,9 @@ enum AccKind : int32_t {
   ACC_MIN_F64 = 3,
   ACC_MAX_F64 = 4,
   ACC_HLL = 5,      // registers, per (group, hll slot)
+  ACC_DISTINCT = 6, // exact DISTINCTCOUNT: a dictionary-id bitmap per (group, distinct slot), filled by distinct.hip.
+                    // Host only: the descriptors the filter / aggregation kernels read carry such a slot as ACC_COUNT
+                    // (a COUNT is row 0 / the matched docs: no kernel accumulates a row for it)
 };
 
 // Device filter-program opcodes (postfix; AND/OR are binary and applied incrementally, so a child
@@ -392,6 +395,29 @@ struct DevSelQuery {
   int32_t num_select;
   int32_t pad;
   DevSelect sel[kMaxSelect];
+};
+
+// Exact DISTINCTCOUNT (distinct.hip): a pass of its own over the filter's tile masks that sets, per matched doc and
+// distinct slot, bit `global id` of the doc's group row in one device bitmap [num_rows][row_words] u32.
+constexpr int kMaxDistinct = kMaxAggs;
+constexpr int kDistinctLdsWords = 8192;  // default PHIP_DISTINCT_LDS_WORDS: 32 KiB of LDS per workgroup
+struct DevDistinctQuery {
+  const DevSeg *segs;
+  int32_t num_segs;
+  int32_t total_work;
+  const uint32_t *mask;  // [total_work][64] lane-major tile masks of the filter kernel; null = every doc
+  uint32_t *bitmap;      // [num_rows][row_words]; bit i of word slot_off[s] + w of a row = global id 32 w + i of slot s
+  int64_t num_rows;      // dense group-by key space (1 without a group-by)
+  int64_t row_words;     // sum over the slots of ceil(card_s / 32)
+  int32_t num_slots;
+  int32_t lds;           // 1: no group-by and row_words fit the LDS budget -- each workgroup ORs into an LDS copy
+  int32_t slot_col[kMaxDistinct];   // the slot's column (DevSeg.cols index)
+  int32_t slot_card[kMaxDistinct];  // its query-global cardinality
+  int64_t slot_off[kMaxDistinct];   // its first word inside a row
+  int32_t num_group_by;
+  int32_t pad;
+  int32_t gb_cols[kMaxGroupBy];
+  int64_t gb_stride[kMaxGroupBy];   // the dense group-by's mixed radix (DevAggQuery.gb_stride)
 };
 
 // ORDER BY on group-by columns for the device trim (trim.hip)

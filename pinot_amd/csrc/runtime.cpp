@@ -90,6 +90,12 @@ hipError_t launch_select_str_bytes(const uint64_t *loc, int64_t rows, const uint
                                    const uint64_t *const *offs, const uint64_t *dst_off, uint8_t *dst, hipStream_t s);
 hipError_t launch_select_gather(const DevSelQuery *q, int64_t total_work, uint64_t *out, int64_t num_rows,
                                 hipStream_t s);
+// distinct.hip (exact DISTINCTCOUNT). Weak: a build of the host code without that file (the host simulation's stub
+// library) links, and a plan that holds a PHIP_AGG_DISTINCT is refused at creation ("distinct pass not built").
+__attribute__((weak)) hipError_t launch_distinct_mark(const DevDistinctQuery *q, int64_t total_work, int lds,
+                                                      size_t lds_bytes, int max_blocks, hipStream_t s);
+__attribute__((weak)) hipError_t launch_distinct_finish(const DevDistinctQuery *q, const int64_t *keys, int64_t num_out,
+                                                        int64_t *counts, uint32_t *out, hipStream_t s);
 hipError_t launch_limit_prepare(const int64_t *slots, int64_t n, const uint64_t *hkeys, const uint32_t *first_doc,
                                 int32_t nseg, uint64_t *sortkey, int32_t *idx, hipStream_t s);
 hipError_t launch_limit_bounds(const uint64_t *sk_sorted, int64_t n, int64_t *first, int64_t *last, hipStream_t s);
@@ -1101,6 +1107,9 @@ struct ResultImpl {
   std::vector<uint64_t> sel_values;  // selection: [num_select][num_rows]
   std::vector<int32_t> sel_types;
   std::vector<std::shared_ptr<Device::Remap>> sel_dicts;  // per select column: query-global dictionary (STRING)
+  std::vector<uint32_t> dist_words;    // DISTINCTCOUNT: [num_groups][dist_offsets.back()] bitmap words
+  std::vector<int64_t> dist_offsets;   // [num_distinct + 1] word offsets of the slots inside a group's row
+  std::vector<std::shared_ptr<Device::Remap>> dist_dicts;  // per distinct slot: its query-global dictionary
   std::vector<int64_t> seg_docs;  // per segment: matched docs summed over the filter programs
   std::vector<int64_t> prog_docs;  // per filter program: matched docs summed over the segments
 };
@@ -1969,6 +1978,7 @@ int acc_kind_for(const phip_aggregation &a, bool integral) {
     case PHIP_AGG_SUM: return integral ? ACC_SUM_I64 : ACC_SUM_F64;
     case PHIP_AGG_MIN: return ACC_MIN_F64;
     case PHIP_AGG_MAX: return ACC_MAX_F64;
+    case PHIP_AGG_DISTINCT: return ACC_DISTINCT;
     default: return ACC_HLL;
   }
 }
@@ -1997,6 +2007,8 @@ struct Plan {
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (dev) (void)hipSetDevice(dev->ordinal);
     for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (auto &e : dist_ev)
       if (e) (void)hipEventDestroy(e);
     for (void *p : allocs) (void)hipFree(p);
     if (pinned) (void)hipHostFree(pinned);
@@ -2102,6 +2114,17 @@ struct Plan {
   std::vector<std::vector<const void *>> sel_str_ptrs;  // per SEL_STR expression: its segments' bytes, then offsets
   std::vector<int32_t> sel_bits, sel_width;  // per select column's projected bytes (algorithmic bytes)
   float sel_filter_ms = 0.f;
+  // exact DISTINCTCOUNT (distinct.hip): slot s = the plan's s-th PHIP_AGG_DISTINCT aggregation (dist_agg[s]); the
+  // descriptor in the blob, the bitmap [dense key space][row words] cleared and filled by every execution
+  int ndist = 0;
+  std::vector<int> dist_agg;
+  std::vector<std::shared_ptr<Device::Remap>> dist_dicts;
+  DevDistinctQuery dstq{};
+  size_t dstq_off = 0;
+  void *dist_bits = nullptr;
+  size_t dist_bytes = 0, dist_lds_bytes = 0;
+  int dist_blocks = 1;
+  hipEvent_t dist_ev[2] = {};  // around the pass (clear + mark kernel): phip_result.distinct_kernel_ms
   // record ev[0] / ev[3] around the whole sequence (phip_result.device_ms): off by default -- every timing marker is a
   // barrier packet the command processor waits on (~4 us each, r04 host A/B); PHIP_TOTAL_EVENTS=1 records them
   bool total_events = false;
@@ -2433,7 +2456,17 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (ag.program < 0 || ag.program >= nprog)
       return fail(PHIP_ERR_INVALID, "aggregation %d: program %d outside [0, %d)", a, ag.program, nprog);
     d.program = ag.program;
-    if (ag.function < PHIP_AGG_COUNT || ag.function > PHIP_AGG_HLL) return fail(PHIP_ERR_INVALID, "bad aggregation function");
+    if (ag.function < PHIP_AGG_COUNT || ag.function > PHIP_AGG_DISTINCT) return fail(PHIP_ERR_INVALID, "bad aggregation function");
+    if (ag.function == PHIP_AGG_DISTINCT) {  // the refusals of include/pinot_hip.h PHIP_AGG_DISTINCT
+      if (launch_distinct_mark == nullptr || launch_distinct_finish == nullptr)
+        return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT: distinct pass not built");
+      if (ag.expr != PHIP_EXPR_COLUMN) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT of an expression");
+      if (nprog > 1) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT beside several filter programs");
+      if (q->null_group_by) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT beside null group keys");
+      if (P.tuple_keys) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over a tuple key space");
+      if (tl_node_docs > 0) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT in a node plan");
+      if (want_bitmap || q->num_select > 0) return fail(PHIP_ERR_INVALID, "DISTINCTCOUNT outside an aggregation query");
+    }
     if (ag.function != PHIP_AGG_COUNT) {
       if (ag.column_a < 0 || ag.column_a >= ncols) return fail(PHIP_ERR_INVALID, "aggregation column out of range");
       projected[ag.column_a] = true;
@@ -2449,6 +2482,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       for (int s = 0; s < nseg; s++) {
         const ColumnStore &ca = segs[s]->cols[colidx[s][ag.column_a]];
         if (!(ca.type == PHIP_TYPE_INT || ca.type == PHIP_TYPE_LONG)) integral = false;
+        if (ag.function == PHIP_AGG_DISTINCT) {  // dictionary ids only: any type, but a dictionary in every segment
+          if (no_dict(ca) || ca.fwd_kind == PHIP_FWD_HLL_REGISTERS || ca.words == nullptr)
+            return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over the raw (no-dictionary) column %s", ca.name.c_str());
+          continue;
+        }
         if (ca.type == PHIP_TYPE_STRING && ag.function != PHIP_AGG_HLL)
           return fail(PHIP_ERR_INVALID, "numeric aggregation over STRING column %s", ca.name.c_str());
         if (ca.fwd_kind == PHIP_FWD_HLL_REGISTERS) {  // star-tree HLL pair: DISTINCTCOUNTHLL of the column only
@@ -2494,6 +2532,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     }
     d.integral = integral;
     d.acc = acc_kind_for(ag, integral);
+    if (d.acc == ACC_DISTINCT) {
+      // its own pass fills its bitmaps (distinct.hip); every other kernel and the result assembly see a COUNT slot,
+      // which none of them accumulates a row for, and the pass's count replaces the slot's value (execute_plan)
+      P.dist_agg.push_back(a);
+      d.acc = ACC_COUNT;
+    }
     kinds[a] = d.acc;
     if (d.acc == ACC_HLL) {
       if (ag.log2m < 4 || ag.log2m > 12) return fail(PHIP_ERR_UNSUPPORTED, "log2m %d outside [4,12]", ag.log2m);
@@ -2535,7 +2579,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         }
       }
       for (int a = 0; a < naggs; a++)
-        if (q->aggregations[a].function == PHIP_AGG_HLL) use_vals[q->aggregations[a].column_a] = false;
+        if (q->aggregations[a].function == PHIP_AGG_HLL || q->aggregations[a].function == PHIP_AGG_DISTINCT)
+          use_vals[q->aggregations[a].column_a] = false;  // (their ids / per-id entries are read)
       for (int k = 0; k < q->num_group_by; k++)
         if (q->group_by_columns[k] >= 0 && q->group_by_columns[k] < ncols) use_vals[q->group_by_columns[k]] = false;
       if (q->filter_offsets && q->filter_nodes)
@@ -2597,7 +2642,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     dq.hist_words = 0;
     {
       const char *he = getenv("PHIP_AGG_HIST");  // measurement override: "0" = gather the values
-      bool ok = q->num_group_by == 0 && dq.dense_batch && nhll == 0 && nprog == 1 && naggs <= 2 && !(he && atoi(he) == 0);
+      bool ok = q->num_group_by == 0 && dq.dense_batch && nhll == 0 && nprog == 1 && naggs <= 2 && !(he && atoi(he) == 0) &&
+                P.dist_agg.empty();
       int col = -1, max_card = 0;
       uint32_t mask = 0;
       for (int a = 0; a < naggs && ok; a++) {
@@ -2633,7 +2679,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     bool ok = dq.dense_batch != 0 && q->num_group_by == 0;
     for (int a = 0; a < naggs && ok; a++) {
       const phip_aggregation &ag = q->aggregations[a];
-      if (ag.function == PHIP_AGG_COUNT) continue;
+      if (ag.function == PHIP_AGG_COUNT || ag.function == PHIP_AGG_DISTINCT) continue;  // (no value read in this walk)
       for (int which = 0; which < 2; which++) {
         const int c = which == 0 ? ag.column_a : (ag.expr != PHIP_EXPR_COLUMN ? ag.column_b : -1);
         if (c < 0) continue;
@@ -2829,6 +2875,51 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     } else {
       dq.num_groups = stride;
     }
+  }
+
+  // exact DISTINCTCOUNT (distinct.hip): one bitmap row per dense group key, one run of words per slot over the
+  // column's query-global dictionary (the per-segment id remap the group-by columns use)
+  DevDistinctQuery dstq;
+  memset(&dstq, 0, sizeof(dstq));
+  if (!P.dist_agg.empty()) {
+    if (group_by && dq.mode == GB_HASH)
+      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over a hash-table group-by key space");
+    for (const auto &gd : gb_dicts)
+      if (gd->raw || !gd->ids.empty()) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over raw group-by keys");
+    dstq.num_slots = (int32_t)P.dist_agg.size();
+    dstq.num_rows = group_by ? dq.num_groups : 1;
+    dstq.num_group_by = q->num_group_by;
+    for (int k = 0; k < q->num_group_by; k++) {
+      dstq.gb_cols[k] = dq.gb_cols[k];
+      dstq.gb_stride[k] = dq.gb_stride[k];
+    }
+    int64_t words = 0;
+    for (int s2 = 0; s2 < dstq.num_slots; s2++) {
+      const int c = q->aggregations[P.dist_agg[s2]].column_a;
+      if (!col_remap[c]) {
+        std::vector<int> ci(nseg);
+        for (int s = 0; s < nseg; s++) ci[s] = colidx[s][c];
+        int32_t rc = build_remap(*dev, segs, ci, q->columns[c], col_remap[c]);
+        if (rc) return rc;
+      }
+      P.dist_dicts.push_back(col_remap[c]);
+      dstq.slot_col[s2] = c;
+      dstq.slot_card[s2] = col_remap[c]->card;
+      dstq.slot_off[s2] = words;
+      words += ceil_div(std::max(col_remap[c]->card, 0), 32);
+    }
+    dstq.row_words = words;
+    const char *mb = getenv("PHIP_DISTINCT_MAX_BYTES");
+    const int64_t max_bytes = mb ? atoll(mb) : (int64_t)256 << 20;
+    if ((long double)dstq.num_rows * (long double)words * 4 > (long double)max_bytes)
+      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT bitmaps of %lld rows x %lld words exceed PHIP_DISTINCT_MAX_BYTES %lld",
+                  (long long)dstq.num_rows, (long long)words, (long long)max_bytes);
+    // LDS regime: no group-by and every slot's words within the budget (default kDistinctLdsWords = 32 KiB per
+    // workgroup: four workgroups stay resident per CU, and a flush is at most 8192 atomics per workgroup); clamped to
+    // 48 KiB, below the 64 KiB a launch may ask for
+    const char *lw = getenv("PHIP_DISTINCT_LDS_WORDS");
+    const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(lw ? atoll(lw) : kDistinctLdsWords, 12288));
+    dstq.lds = (!group_by && words <= lds_words) ? 1 : 0;
   }
 
   // ---- staging blob: segments, nodes, leaf aux ------------------------------------------------
@@ -3229,6 +3320,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       }
     }
   }
+  // (the re-size above may have turned a large dense key space into a hash table after the first check)
+  if (!P.dist_agg.empty() && group_by && dq.mode == GB_HASH)
+    return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over a hash-table group-by key space");
   dq.num_segs = (int32_t)dsegs.size();
   const size_t segs_off = blob.reserve(sizeof(DevSeg) * std::max<size_t>(dsegs.size(), 1));
 
@@ -3321,7 +3415,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   for (const DevSeg &ds : dsegs) has_filter |= ds.node_end > ds.node_begin;
   bool need_agg = group_by || nprog > 1;  // several programs: every COUNT is per program, in the aggregation walk
   for (int a = 0; a < naggs; a++) need_agg |= dq.aggs[a].acc != ACC_COUNT;
-  bool need_mask = has_filter && (need_agg || want_bitmap || nsel > 0);
+  const int ndist = (int)P.dist_agg.size();  // (the distinct pass reads the tile masks as the aggregation walk does)
+  bool need_mask = has_filter && (need_agg || want_bitmap || nsel > 0 || ndist > 0);
   const int64_t kSlotBudget = 19 * 1024;  // bytes per ring slot
   int32_t stage_stride = 0;
   std::vector<double> seg_est(dsegs.size(), 1.0);
@@ -3579,7 +3674,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     bool bs_all = true;  // (the P-layout conjunction's heavier evaluation keeps the size rule)
     for (const DevSeg &ds : dsegs) bs_all &= ds.conj == 0 || ds.conj_bs != 0;
     const bool fuse_large = (fl ? atoi(fl) != 0 : true) && bs_all;
+    // (a DISTINCTCOUNT plan takes the unfused route: its pass needs the tile masks)
     bool fuse = conj_all && any_filter_prog && !group_by && nprog == 1 && nhll == 0 && naggs > 0 && naggs <= 4 && !want_bitmap &&
+                ndist == 0 &&
                 (fe ? atoi(fe) != 0 : (!dense_small && (!big || fuse_large || (fuse_per_tile > 0 && per_tile <= fuse_per_tile))));
     bool any_value = false;
     for (int a = 0; a < naggs; a++) any_value |= dq.aggs[a].acc != ACC_COUNT;
@@ -3654,7 +3751,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // 0.985 ms, Q3.1 0.955 -> 1.670, Q4.2 0.628 -> 1.323, Q4.1 0.780 -> 0.765 (profiles/r05t_lds_ab.log) -- opt-in only.
   bool fused_gb = false, gb_xcd = false, gb_lds = false;
   int64_t gb_lds_bytes = 0;  // the fused LDS table per workgroup
-  if (group_by && dq.mode != GB_HASH && conj_all && any_filter_prog && nprog == 1 && !want_bitmap && nsel == 0) {
+  if (group_by && dq.mode != GB_HASH && conj_all && any_filter_prog && nprog == 1 && !want_bitmap && nsel == 0 &&
+      ndist == 0) {
     const char *fg = getenv("PHIP_FUSED_GB");
     const int fgm = fg ? atoi(fg) : 1;
     const int64_t m = nhll ? ((int64_t)1 << log2m) : 0;
@@ -3903,6 +4001,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   const size_t kinds_off = blob.add(kinds.data(), kinds.size() * 4);
   const size_t dq_off = blob.reserve(sizeof(DevAggQuery));  // written once every pointer is known
   const size_t sq_off = nsel > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
+  const size_t dstq_off = ndist > 0 ? blob.reserve(sizeof(DevDistinctQuery)) : 0;
 
   void *dblob;
   int32_t rc = P.alloc(blob.data.size() + 64, &dblob);
@@ -4017,6 +4116,24 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   }
 
   memcpy(blob.data.data() + dq_off, &dq, sizeof(dq));
+  if (ndist > 0) {
+    P.dist_bytes = (size_t)dstq.num_rows * (size_t)dstq.row_words * 4;
+    rc = P.alloc(P.dist_bytes, &P.dist_bits);
+    if (rc) return rc;
+    dstq.segs = dev_segs;
+    dstq.num_segs = (int32_t)dsegs.size();
+    dstq.total_work = (int32_t)total_work;
+    dstq.mask = need_mask ? (const uint32_t *)masks : nullptr;
+    dstq.bitmap = (uint32_t *)P.dist_bits;
+    memcpy(blob.data.data() + dstq_off, &dstq, sizeof(dstq));
+    P.ndist = ndist;
+    P.dstq = dstq;
+    P.dstq_off = dstq_off;
+    P.dist_lds_bytes = dstq.lds ? (size_t)round_up(std::max<int64_t>(dstq.row_words, 1) * 4, 16) : 0;
+    // the LDS regime flushes once per workgroup: no more workgroups than stay resident; the global one spreads wider
+    P.dist_blocks = dev->num_cus * (dstq.lds ? 4 : 8);
+    for (auto &e : P.dist_ev) HIP_TRY(hipEventCreate(&e));
+  }
   if (nsel > 0) {
     void *sb;
     const size_t nent = dsegs.size();
@@ -4133,6 +4250,27 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     P.order_desc = q->order_by_desc ? 1 : 0;
     P.trim_size = q->trim_size;
   }
+  if (P.ndist > 0 && q->trim_size > 0) {
+    // The device trim sorts the table's rows, and a DISTINCTCOUNT's value is not in them. An ORDER BY term on one is
+    // accepted only when the dense key space fits trim_size: the trim can then never fire (groups <= key space), and
+    // ordering is the broker reduce's job as for every untrimmed result.
+    auto is_dist = [&](int32_t i) {
+      return i >= 0 && i < q->num_aggregations && q->aggregations[i].function == PHIP_AGG_DISTINCT;
+    };
+    bool on_distinct = false;
+    if (q->num_order_terms > 0 && q->order_terms) {
+      for (int j = 0; j < q->num_order_terms; j++) {
+        const phip_order_term &t = q->order_terms[j];
+        if (t.kind == PHIP_ORDER_GROUP_KEY) continue;
+        on_distinct |= is_dist(t.a) || ((t.kind == PHIP_ORDER_AVG || t.kind == PHIP_ORDER_RANGE) && is_dist(t.b));
+      }
+    } else if (q->num_order_by_keys <= 0) {
+      on_distinct = is_dist(q->order_by_aggregation);
+    }
+    if (on_distinct && gb_key_space > q->trim_size)  // (the dense key space itself, whatever the table's placement)
+      return fail(PHIP_ERR_UNSUPPORTED, "ORDER BY a DISTINCTCOUNT over a key space of %lld above trim_size %lld",
+                  (long long)gb_key_space, (long long)q->trim_size);
+  }
   P.total_work = total_work;
   P.total_docs = total_docs;
   P.docs_in_work = 0;
@@ -4216,7 +4354,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // its partials' acknowledgement and a ticket before it retires, and the fused kernel itself grows 11 % (sorted Q1.1
   // 0.135 -> 0.150 ms): its own roofline fraction drops more than the step gains. Opt-in (PHIP_FOLD_FINAL=1).
   const char *ff = getenv("PHIP_FOLD_FINAL");
-  if (!group_by && !P.select && !want_bitmap && total_work > 0 && (has_filter || need_agg) && ff && atoi(ff) != 0) {
+  if (!group_by && !P.select && !want_bitmap && total_work > 0 && (has_filter || need_agg) && ff && atoi(ff) != 0 &&
+      P.ndist == 0) {
     const bool fused = fused_naggs > 0;
     const bool agg_last = need_agg && !fused;
     const bool aggs_here = need_agg && naggs > 0;
@@ -4338,6 +4477,15 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   if (need_agg && total_work > 0 && !fused)
     HIP_TRY(launch_agg(dq, (const DevAggQuery *)(base + dq_off), agg_blocks, agg_lds, st, e0, e1));
   if (!ext_events && P.timed) HIP_TRY(hipEventRecord(P.ev[2], st));
+  if (P.ndist > 0) {
+    // the distinct pass (distinct.hip): its bitmaps cleared inside the sequence, so a re-execution and a replayed
+    // graph start clean; popcounts and the rows' gather follow the host's group list (execute_plan distinct_finish)
+    if (P.timed) HIP_TRY(hipEventRecord(P.dist_ev[0], st));
+    HIP_TRY(hipMemsetAsync(P.dist_bits, 0, std::max<size_t>(P.dist_bytes, 16), st));
+    HIP_TRY(launch_distinct_mark((const DevDistinctQuery *)(base + P.dstq_off), total_work, P.dstq.lds, P.dist_lds_bytes,
+                                 P.dist_blocks, st));
+    if (P.timed) HIP_TRY(hipEventRecord(P.dist_ev[1], st));
+  }
   if (group_by && P.gb_xcd && total_work > 0)  // the XCD-private copies folded into copy 0 (the plan's table)
     HIP_TRY(launch_xcd_merge((uint64_t *)gtab, dq.xcd_words, dq.num_groups, dev_kinds, (uint32_t *)ghll,
                              dq.xcd_hll_words, st));
@@ -4651,10 +4799,48 @@ static_assert(ACC_COUNT == PHIP_ROW_COUNT && ACC_SUM_I64 == PHIP_ROW_SUM_I64 && 
               "partial row kinds are the accumulator kinds");
 static_assert(kMaxAggs + 1 <= PHIP_PARTIAL_MAX_ROWS, "phip_partial.row_kinds holds every row");
 
+// The distinct pass's second half (distinct.hip distinct_finish_kernel), once the host knows the groups the result
+// returns (after compaction, the numGroupsLimit pass and the trim): keys = their dense keys (null: the one row of an
+// aggregation-only plan). Per group and slot the popcount becomes the aggregation's value; the rows are gathered back
+// to back into the result. One more host wait per execution of a plan that holds a DISTINCTCOUNT.
+static int32_t distinct_finish(Plan &P, Workspace &ws, hipStream_t st, ResultImpl &impl, const std::vector<int64_t> *keys,
+                               int64_t ngroups) {
+  const int ns = P.ndist, naggs = P.naggs;
+  const int64_t rw = P.dstq.row_words;
+  impl.dist_offsets.assign(ns + 1, 0);
+  for (int s = 0; s < ns; s++) impl.dist_offsets[s] = P.dstq.slot_off[s];
+  impl.dist_offsets[ns] = rw;
+  impl.dist_dicts = P.dist_dicts;
+  impl.dist_words.assign((size_t)ngroups * (size_t)rw, 0u);
+  if (ngroups <= 0) return PHIP_OK;
+  const size_t kb = keys ? (size_t)ngroups * 8 : 0, cb = (size_t)ngroups * ns * 8, wb = (size_t)ngroups * (size_t)rw * 4;
+  void *buf;
+  int32_t rc = ws.get("distinct_out", std::max<size_t>(kb + cb + wb, 16), &buf);
+  if (rc) return rc;
+  int64_t *dkeys = keys ? (int64_t *)buf : nullptr;
+  int64_t *dcounts = (int64_t *)((uint8_t *)buf + kb);
+  uint32_t *dwords = (uint32_t *)((uint8_t *)buf + kb + cb);
+  if (keys) HIP_TRY(hipMemcpyAsync(dkeys, keys->data(), kb, hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_distinct_finish((const DevDistinctQuery *)(P.base + P.dstq_off), dkeys, ngroups, dcounts, dwords, st));
+  std::vector<int64_t> counts((size_t)ngroups * ns);
+  HIP_TRY(hipMemcpyAsync(counts.data(), dcounts, cb, hipMemcpyDeviceToHost, st));
+  if (wb) HIP_TRY(hipMemcpyAsync(impl.dist_words.data(), dwords, wb, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t g = 0; g < ngroups; g++)
+    for (int s = 0; s < ns; s++) {
+      const int64_t n = counts[(size_t)g * ns + s];
+      impl.values[(size_t)g * naggs + P.dist_agg[s]] = (double)n;
+      impl.longs[(size_t)g * naggs + P.dist_agg[s]] = n;
+    }
+  return PHIP_OK;
+}
+
 static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_words, int mode = EXEC_FULL,
                             phip_partial *part = nullptr, const phip_partial *merged = nullptr) {
   Device *dev = P.dev;
   std::lock_guard<std::mutex> xlock(P.exec_mu);
+  if (mode != EXEC_FULL && P.ndist > 0)
+    return fail(PHIP_ERR_UNSUPPORTED, "partial tables: a plan with a DISTINCTCOUNT has no mergeable table");
   // (a node part's hash table goes out too: node.cpp inserts the other parts' groups into the root's table)
   if (mode != EXEC_FULL && (!P.group_by || (P.dq.mode == GB_HASH && !P.node_part)))
     return fail(PHIP_ERR_UNSUPPORTED, "partial tables: dense group-by and aggregation plans only (this plan: %s)",
@@ -4792,6 +4978,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   }
 
   int64_t ngroups = 1;
+  std::vector<int64_t> dist_keys;  // DISTINCTCOUNT: the returned groups' dense keys (their bitmap rows)
   if (group_by) {
     const int64_t nchunks = ceil_div(dq.num_groups, 1024);
     void *cc, *offs, *keys;
@@ -4882,6 +5069,12 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     // some segment may have reached numGroupsLimit: the first-seen pass decides which keys it kept (and the
     // normal pass's compaction would be thrown away)
     const bool limit_pass = mode == EXEC_FULL && P.num_groups_limit > 0 && ngroups >= P.num_groups_limit;
+    // The limit pass is per segment: a segment that dropped a key skips that key's docs (DefaultGroupByExecutor), so a
+    // kept group's values come only from the segments that kept it. The distinct bitmaps hold one row per key over
+    // every segment's docs, which is that answer for one segment only: with several the CPU plan maker answers.
+    if (limit_pass && P.ndist > 0 && nseg > 1)
+      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT: %lld groups reach numGroupsLimit %lld over %d segments",
+                  (long long)ngroups, (long long)P.num_groups_limit, nseg);
     // the compacted keys, values, exact sums and registers of the groups back to back in one buffer (one copy out)
     auto contiguous_out = [&](const char *name, int64_t n, void **k, void **v, void **l, void **h) -> int32_t {
       void *base;
@@ -4998,6 +5191,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
       if (hb) memcpy(impl->hll.data(), staged.data() + kb + 2 * vb, hb);
     }
     if (overflow) return kGrowHash;
+    if (P.ndist > 0) dist_keys = hkeys;
     impl->keys.resize(ngroups * P.num_group_by);
     for (int64_t g = 0; g < ngroups; g++) {
       int64_t key = hkeys[g];
@@ -5113,6 +5307,17 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
       impl->longs[a] = l;
     }
     if (nhll) for (size_t i = 0; i < ((size_t)nhll << log2m); i++) impl->hll[i] = (uint8_t)hll_host[i];
+  }
+  if (P.ndist > 0) {
+    if ((rc = distinct_finish(P, ws, st, *impl, group_by ? &dist_keys : nullptr, group_by ? ngroups : 1))) return rc;
+    r.num_distinct = P.ndist;
+    r.distinct_words = impl->dist_words.data();
+    r.distinct_word_offsets = impl->dist_offsets.data();
+    if (P.timed && !P.graph_exec) {
+      float t_d = 0.f;
+      HIP_TRY(hipEventElapsedTime(&t_d, P.dist_ev[0], P.dist_ev[1]));
+      r.distinct_kernel_ms = t_d;
+    }
   }
   float t_all = 0.f, t_scan = 0.f, t_filter = 0.f, t_agg = 0.f;
   if (P.timed && total_work > 0) HIP_TRY(hipEventElapsedTime(&t_scan, P.ev[1], P.ev[2]));
@@ -5289,6 +5494,8 @@ static int32_t agg_partial_buffers(Plan &P) {
 
 static int32_t execute_agg_partial(Plan &P, phip_partial *part) {
   if (P.select || P.naggs > kMaxAggs) return fail(PHIP_ERR_UNSUPPORTED, "partial tables: not for selection plans");
+  if (P.ndist > 0)
+    return fail(PHIP_ERR_UNSUPPORTED, "partial tables: a plan with a DISTINCTCOUNT has no mergeable table");
   phip_result *res = nullptr;
   int32_t rc = execute_plan(P, &res, nullptr, EXEC_FULL);  // (refuses while a partial is pending)
   if (rc) return rc;
@@ -5801,6 +6008,19 @@ PHIP_API int32_t phip_result_dictionary(const phip_result *result, int32_t k, ph
   const ResultImpl *impl = reinterpret_cast<const ResultImpl *>(result);
   if (k < 0 || k >= (int)impl->dicts.size()) return fail(PHIP_ERR_INVALID, "group-by index out of range");
   const auto &d = impl->dicts[k];
+  out->data_type = d->type;
+  out->cardinality = d->card;
+  out->string_width = d->width;
+  out->reserved = 0;
+  out->values = d->values.data();
+  return PHIP_OK;
+}
+
+PHIP_API int32_t phip_result_distinct_dictionary(const phip_result *result, int32_t k, phip_dictionary_view *out) {
+  if (!result || !out) return fail(PHIP_ERR_INVALID, "null argument");
+  const ResultImpl *impl = reinterpret_cast<const ResultImpl *>(result);
+  if (k < 0 || k >= (int)impl->dist_dicts.size()) return fail(PHIP_ERR_INVALID, "distinct index out of range");
+  const auto &d = impl->dist_dicts[k];
   out->data_type = d->type;
   out->cardinality = d->card;
   out->string_width = d->width;

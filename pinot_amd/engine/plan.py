@@ -32,6 +32,7 @@ from ..query.sql import parse
 from ..spi import (DEFAULT_GROUPBY_TRIM_THRESHOLD, DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE,
                    DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE, DEFAULT_NUM_GROUPS_LIMIT, MAX_TRIM_THRESHOLD, DataType)
 from .results import (AggregationResultsBlock, ExecutionStatistics, GroupByResultsBlock, SelectionResultsBlock,
+                      java_double_key,
                       merge_intermediate)
 from .segment import GpuSegment
 
@@ -458,6 +459,15 @@ def plan_aggregations(aggs: Sequence[AggregationInfo], programs: Optional[Sequen
         elif f in ("distinctcounthll", "distinctcountrawhll"):
             # (over an expression: its DOUBLE values hashed on the device, as the reference offers a transform's result)
             mapping.append((f, slot((_lib.AGG_HLL,) + expr + (ag.log2m,))))
+        elif f == "distinctcount":
+            # exact: one bitmap of query-global dictionary ids per column (PHIP_AGG_DISTINCT); the same column twice
+            # shares the primitive. Arguments outside a plain column, and other filter programs beside it (FILTER
+            # clauses, CASE branches, the null-handling programs), stay with the CPU plan maker.
+            if expr[0] != _lib.EXPR_COLUMN:
+                raise UnsupportedOnGpu("distinctcount of an expression is not on the GPU path")
+            if programs is not None:
+                raise UnsupportedOnGpu("distinctcount beside FILTER / CASE / null-handling filter programs")
+            mapping.append((f, slot((_lib.AGG_DISTINCT,) + expr + (0,))))
         else:
             raise UnsupportedOnGpu(f"aggregation {f} is not on the GPU path")
     return prims, mapping
@@ -486,6 +496,16 @@ class GpuCombineOperator:
         self.stats_programs = 0  # phip_query_desc.stats_programs: 0 = every program's scans count
         self.prims, self.mapping = plan_aggregations(query.aggregations, programs[1] if programs is not None else None)
         nh = null_handling_enabled(query)
+        for p in self.prims:
+            if p[0] != _lib.AGG_DISTINCT:
+                continue
+            if nh:
+                raise UnsupportedOnGpu("distinctcount with enableNullHandling")
+            if segment_filters is not None:
+                raise UnsupportedOnGpu("distinctcount over a star-tree's documents")
+            for s in self.segments:
+                if s.has_column(p[2]) and not s.column_metadata(p[2]).has_dictionary:
+                    raise UnsupportedOnGpu(f"distinctcount over the raw (no-dictionary) column {p[2]}")
         # enableNullHandling: the group-by columns whose null docs key as the null key (phip_query_desc.null_group_by;
         # NoDictionary*GroupKeyGenerator with null handling, DefaultGroupByExecutor.java:106-116)
         self.null_keys = 0
@@ -635,7 +655,7 @@ class GpuCombineOperator:
                 terms.append((_lib.ORDER_RANGE, int(sl[0]), int(sl[1]), desc))
             elif f == "distinctcounthll":  # (its cardinality estimate, computed from the registers on the device)
                 terms.append((_lib.ORDER_HLL, int(sl), 0, desc))
-            else:
+            else:  # (distinctcount too: its counts are not in the device table's rows, the broker reduce orders them)
                 return none
         if len(terms) == 1 and terms[0][0] == _lib.ORDER_VALUE:
             return terms[0][1], terms[0][3], trim, [], []
@@ -704,7 +724,7 @@ class GpuCombineOperator:
             pass
 
     # -- NonScanBasedAggregationOperator (AggregationPlanNode.java:107-118, isFitForNonScanBasedPlan :165-190)
-    _NON_SCAN = ("count", "min", "max", "minmaxrange", "distinctcounthll", "distinctcountrawhll")
+    _NON_SCAN = ("count", "min", "max", "minmaxrange", "distinctcounthll", "distinctcountrawhll", "distinctcount")
 
     def _non_scan_fit(self):
         if self.query.group_by or not all(_is_const(t, _TRUE) for t in self.trees):
@@ -742,6 +762,8 @@ class GpuCombineOperator:
                     seg_res.append(float(d.get(len(d) - 1)))
                 elif ag.function == "minmaxrange":
                     seg_res.append((float(d.get(0)), float(d.get(len(d) - 1))))
+                elif ag.function == "distinctcount":  # (NonScanBasedAggregationOperator.java:106-113: the dictionary)
+                    seg_res.append(_distinct_value_set(np.asarray(d.values)))
                 else:
                     seg_res.append(hll.registers_of_hashes(hll.hash_values(d.values, d.data_type), ag.log2m))
             if results is None:
@@ -798,7 +820,7 @@ class GpuCombineOperator:
         None: the general path applies."""
         f = _lib.RESULT_IMAGE.unpack(ctypes.string_at(res, _lib.RESULT_IMAGE.size))
         na, ng, nhll = f[7], f[8], f[10]
-        if ng != 1 or nhll:
+        if ng != 1 or nhll or f[32]:  # (HLL registers / DISTINCTCOUNT bitmaps: the general decode)
             return None
         dec = self.__dict__.get("_agg_dec")
         if dec is None or dec[0] != na:  # (per operator: the slots' structs and each primitive's kind)
@@ -820,6 +842,30 @@ class GpuCombineOperator:
         blk.stream_bytes = f[30]
         blk.segment_docs_matched = None
         return blk
+
+    def _distinct_sets(self, lib, res, r, ng):
+        """{primitive index: [per group the set of the column's values]} of a result's DISTINCTCOUNT slots
+        (phip_result.distinct_words over phip_result_distinct_dictionary): slot s is the s-th AGG_DISTINCT primitive."""
+        nd = int(r.num_distinct)
+        offs = [int(r.distinct_word_offsets[i]) for i in range(nd + 1)]
+        rw = offs[nd]
+        words = (np.ctypeslib.as_array(r.distinct_words, shape=(ng * rw,)).reshape(ng, rw) if ng * rw
+                 else np.zeros((ng, rw), np.uint32))
+        out = {}
+        slots = [i for i, p in enumerate(self.prims) if p[0] == _lib.AGG_DISTINCT]
+        for s, i in enumerate(slots):
+            dv = _lib.DictionaryView()
+            _lib.check(lib.phip_result_distinct_dictionary(res, s, ctypes.byref(dv)))
+            w = np.ascontiguousarray(words[:, offs[s]:offs[s + 1]])
+            if w.shape[1] == 0:
+                out[i] = [set() for _ in range(ng)]
+                continue
+            bits = np.unpackbits(w.view(np.uint8), axis=1, bitorder="little")  # bit i of word w = id 32 w + i
+            rows, ids = np.nonzero(bits)
+            vals = _dictionary_array(dv, ids)
+            cuts = np.searchsorted(rows, np.arange(ng + 1))
+            out[i] = [_distinct_value_set(vals[cuts[g]:cuts[g + 1]]) for g in range(ng)]
+        return out
 
     def _key_values(self, k, dv, ids):
         """Values of group-by column k's keys (`ids` into the result's query-global dictionary) as an array; under
@@ -894,6 +940,8 @@ class GpuCombineOperator:
                 hll = np.ctypeslib.as_array(r.hll_registers, shape=(ng * r.num_hll * m,)).reshape(ng, r.num_hll, m).copy()
             # long_exact[a]: the library kept an exact int64 sum (else it summed in double: int64 overflow bound)
             exact = [bool(r.long_exact[i]) for i in range(na)] if na else []
+            # DISTINCTCOUNT: per primitive the groups' value sets, from the bitmaps over the slot's dictionary
+            dsets = self._distinct_sets(lib, res, r, ng) if r.num_distinct else {}
 
             def prim_value(g, i):
                 f = self.prims[i][0]
@@ -903,6 +951,8 @@ class GpuCombineOperator:
                     return int(longs[g][i]) if exact[i] else float(vals[g][i])
                 if f in (_lib.AGG_MIN, _lib.AGG_MAX):
                     return float(vals[g][i])
+                if f == _lib.AGG_DISTINCT:
+                    return dsets[i][g]
                 return hll[g, hll_slot[i], :1 << self.prims[i][4]].copy()  # (slots hold 2^max-log2m bytes)
 
             def intermediates(g):
@@ -937,6 +987,10 @@ class GpuCombineOperator:
                         prim_arrays.append(longs[:, i].copy())
                     elif f in (_lib.AGG_SUM, _lib.AGG_MIN, _lib.AGG_MAX):
                         prim_arrays.append(vals[:, i].copy())
+                    elif f == _lib.AGG_DISTINCT:
+                        col = np.empty(ng, dtype=object)
+                        col[:] = dsets[i]
+                        prim_arrays.append(col)
                     else:
                         mi = 1 << self.prims[i][4]
                         prim_arrays.append(hll[:, hll_slot[i], :mi] if hll is not None  # (hll is a copy)
@@ -961,6 +1015,15 @@ class GpuCombineOperator:
             return blk
         finally:
             lib.phip_result_free(res)
+
+
+def _distinct_value_set(values):
+    """A DISTINCTCOUNT intermediate: the set of `values` (a numpy array, or a list of str). FLOAT / DOUBLE members
+    compare by their bits, as the reference's FloatOpenHashSet / DoubleOpenHashSet do: -0.0 and 0.0 are two members,
+    every NaN is one (results.java_double_key)."""
+    if isinstance(values, np.ndarray) and values.dtype.kind == "f":
+        return {java_double_key(v) for v in values.tolist()}
+    return set(values.tolist() if isinstance(values, np.ndarray) else values)
 
 
 def _string_cache_lookup(cache, k, dv, ids):
@@ -2206,6 +2269,9 @@ class GpuInstancePlanMaker:
             return st
         if query.is_selection:
             return GpuSelectionOperator(query, segments, limit)
+        if any(ag.function == "distinctcount" for ag in query.aggregations) and any(
+                ag.filter is not None or (ag.argument is not None and _is_case(ag.argument)) for ag in query.aggregations):
+            raise UnsupportedOnGpu("distinctcount in a query with FILTER clauses or CASE aggregations")
         if any(ag.argument is not None and _is_case(ag.argument) for ag in query.aggregations):
             return GpuCaseAggregationOperator(query, segments, limit)
         if any(ag.filter is not None for ag in query.aggregations):

@@ -72,6 +72,8 @@ def final_result(function: str, v):
         return float(v[1]) - float(v[0])
     if function in ("distinctcounthll", "distinctcountrawhll"):
         return hll_cardinality(v)
+    if function == "distinctcount":  # (DistinctCountAggregationFunction.extractFinalResult: the set's size, INT)
+        return int(len(v))
     raise NotImplementedError(function)
 
 

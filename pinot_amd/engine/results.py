@@ -7,7 +7,8 @@
 
 Intermediate results follow each function's intermediate type:
   count -> int, sum -> float (int when every input is INT/LONG: exact), min/max ->
-  float, avg -> (sum, count), minmaxrange -> (min, max), distinctcounthll -> uint8 registers.
+  float, avg -> (sum, count), minmaxrange -> (min, max), distinctcounthll -> uint8 registers,
+  distinctcount -> set of the column's values (FLOAT / DOUBLE members keyed by their bits: java_double_key).
 """
 import math
 from dataclasses import dataclass, field
@@ -175,4 +176,6 @@ def merge_intermediate(function: str, a, b):
         return (min(a[0], b[0]), max(a[1], b[1]))
     if function in ("distinctcounthll", "distinctcountrawhll"):
         return np.maximum(a, b)
+    if function == "distinctcount":  # value sets (BaseDistinctAggregateAggregationFunction.merge: addAll)
+        return a | b
     raise NotImplementedError(function)
