@@ -422,12 +422,13 @@ def _expr_values(os_, e, docs):
             return _case_values(os_, e, docs, lambda x: _expr_values(os_, x, docs).astype(np.float64), np.float64)
         a = _expr_values(os_, e.args[0], docs).astype(np.float64)
         b = _expr_values(os_, e.args[1], docs).astype(np.float64)
-        if e.name == "times":
-            return 1.0 * a * b  # MultiplicationTransformFunction.java:90-106
-        if e.name == "minus":
-            return a - b
-        if e.name == "plus":
-            return a + b
+        with np.errstate(invalid="ignore", over="ignore"):  # (0 * inf, inf - inf: NaN, as Java computes them)
+            if e.name == "times":
+                return 1.0 * a * b  # MultiplicationTransformFunction.java:90-106
+            if e.name == "minus":
+                return a - b
+            if e.name == "plus":
+                return a + b
         if e.name == "divide":
             return a / b
     raise NotImplementedError(str(e))
@@ -556,16 +557,52 @@ def _agg_segment(os_, ag, docs, null_handling=False):
         ex = _exact_values(os_, ag.argument, docs)
         return s, (_exact_sum(ex) if ex is not None else None)
     if f == "min":
-        return (float(vals.min()) if len(vals) else float("inf")), None
+        return _math_min_max(vals)[0], None
     if f == "max":
-        return (float(vals.max()) if len(vals) else float("-inf")), None
+        return _math_min_max(vals)[1], None
     if f == "avg":
         s = _oracle_lib().oracle_block_sum_f64(np.ascontiguousarray(vals).ctypes.data, len(vals), MAX_DOC_PER_CALL)
         return (s, len(vals)), None
     if f == "minmaxrange":
-        return ((float(vals.min()) if len(vals) else float("inf")),
-                (float(vals.max()) if len(vals) else float("-inf"))), None
+        one = np.zeros(len(vals), dtype=np.int64)
+        mn, mx = _compare_min_max(vals, one, 1)
+        return (float(mn[0]), float(mx[0])), None
     raise NotImplementedError(f)
+
+
+def _math_min_max(vals):
+    """(min, max) as MinAggregationFunction.aggregate / MaxAggregationFunction.aggregate fold them with Math.min /
+    Math.max (:117-130,151-160): NaN when any value is NaN, -0.0 below 0.0; +inf / -inf over no values."""
+    if len(vals) == 0:
+        return float("inf"), float("-inf")
+    if np.isnan(vals).any():
+        return float("nan"), float("nan")
+    mn, mx = float(vals.min()), float(vals.max())
+    if mn == 0.0:
+        mn = -0.0 if (np.signbit(vals) & (vals == 0)).any() else 0.0
+    if mx == 0.0:
+        mx = 0.0 if (~np.signbit(vals) & (vals == 0)).any() else -0.0
+    return mn, mx
+
+
+def _compare_min_max(vals, gid, ng):
+    """Per-group (min, max) arrays as the comparing holders update them in doc order -- ``value < holder`` /
+    ``value > holder`` from +inf / -inf (MinAggregationFunction.aggregateGroupBySV :180-188, MinMaxRangePair.apply
+    :42-49): a NaN never replaces the holder, and of two zeros the first seen stays."""
+    mn = np.full(ng, np.inf)
+    mx = np.full(ng, -np.inf)
+    keep = ~np.isnan(vals)
+    vals, gid = vals[keep], np.asarray(gid)[keep]
+    np.minimum.at(mn, gid, vals)
+    np.maximum.at(mx, gid, vals)
+    zero = np.nonzero(vals == 0)[0]
+    if len(zero):  # (docs ascend, so np.unique's first index per group is its first zero in doc order)
+        zg, first = np.unique(gid[zero], return_index=True)
+        fz = vals[zero[first]]
+        for out in (mn, mx):
+            sel = out[zg] == 0
+            out[zg[sel]] = fz[sel]
+    return mn, mx
 
 
 def _group_segment(os_, query, docs, num_groups_limit, null_handling=False):
@@ -643,7 +680,8 @@ def _group_aggregate(os_, ag, docs, gid, ng):
         vals = _expr_values(os_, ag.argument, docs).astype(np.float64)
         if f in ("sum", "avg"):
             acc = np.zeros(ng)
-            np.add.at(acc, gid, vals)               # sequential, doc order within a group
+            with np.errstate(invalid="ignore", over="ignore"):  # (inf - inf, overflow to inf: IEEE, as in Java)
+                np.add.at(acc, gid, vals)           # sequential, doc order within a group
             sums = acc.tolist()
             if f == "sum":
                 e = _exact_values(os_, ag.argument, docs)
@@ -660,10 +698,7 @@ def _group_aggregate(os_, ag, docs, gid, ng):
             else:
                 v = list(zip(sums, np.bincount(gid, minlength=ng).tolist()))
         elif f in ("min", "max", "minmaxrange"):
-            mn = np.full(ng, np.inf)
-            mx = np.full(ng, -np.inf)
-            np.minimum.at(mn, gid, vals)
-            np.maximum.at(mx, gid, vals)
+            mn, mx = _compare_min_max(vals, gid, ng)
             v = mn.tolist() if f == "min" else (mx.tolist() if f == "max" else list(zip(mn.tolist(), mx.tolist())))
         else:
             raise NotImplementedError(f)

@@ -545,6 +545,30 @@ class GpuCombineOperator:
             for c in cols:
                 if not s.has_column(c):
                     raise KeyError(f"segment {s.name} has no column {c}")
+        self._refuse_nan_extrema()
+
+    def _refuse_nan_extrema(self):
+        """MIN / MAX / MINMAXRANGE whose values can be NaN stay with the CPU plan maker. The reference's answer then
+        depends on the operator -- Math.min / Math.max propagate a NaN without GROUP BY, the group-by holders and
+        MinMaxRangePair compare and never take one, the merge ``r1 < r2 ? r1 : r2`` keeps the later NaN -- while the
+        kernels drop a NaN in fmin / fmax and order it by its sign bit in the tables' unsigned atomics. Decided from
+        what the segments know (GpuSegment.real_specials): a plain column that holds NaN, or under arithmetic one that
+        holds NaN or an infinity (0 * inf, inf - inf). SUM / AVG add NaN and infinities as IEEE does and stay; so does
+        a query the dictionaries answer (_non_scan_fit: NonScanBasedAggregationOperator reads no value)."""
+        extrema = [p for p in self.prims if p[0] in (_lib.AGG_MIN, _lib.AGG_MAX)]
+        if not extrema or self._non_scan_fit():
+            return
+        for p in extrema:
+            arithmetic = p[1] != _lib.EXPR_COLUMN
+            for c in (p[2], p[3]):
+                for s in self.segments if c is not None else ():
+                    nan, inf = s.real_specials(c)
+                    if nan:
+                        raise UnsupportedOnGpu(f"MIN / MAX / MINMAXRANGE over column {c}, which holds NaN in segment "
+                                               f"{s.name}")
+                    if inf and arithmetic:
+                        raise UnsupportedOnGpu(f"MIN / MAX / MINMAXRANGE over arithmetic on column {c}, which holds an "
+                                               f"infinity in segment {s.name}: its values can be NaN")
 
     def _desc(self, keep):
         col_index = {c: i for i, c in enumerate(self.columns)}
@@ -1566,15 +1590,19 @@ class GpuCaseAggregationOperator:
                     acc = float(acc)
                 out.append(acc if fn == "sum" else (acc, int(vals[total])))
                 continue
+            # the branches' results merge as intermediates do (results.merge_intermediate: the reference's
+            # comparison merges, the earlier branches the running result), from the holder defaults
             lo, hi = float("inf"), float("-inf")
             for kind, x, s in branches:
-                if kind == "lit":
-                    if vals[s] > 0:
-                        lo, hi = min(lo, float(x)), max(hi, float(x))
-                elif fn == "minmaxrange":
-                    lo, hi = min(lo, vals[s][0]), max(hi, vals[s][1])
+                if kind == "lit" and not vals[s] > 0:
+                    continue
+                v = vals[s] if kind == "expr" else (float(x), float(x)) if fn == "minmaxrange" else float(x)
+                if fn == "minmaxrange":
+                    lo, hi = merge_intermediate("minmaxrange", (lo, hi), v)
+                elif fn == "min":
+                    lo = merge_intermediate("min", lo, v)
                 else:
-                    lo, hi = min(lo, vals[s]), max(hi, vals[s])
+                    hi = merge_intermediate("max", hi, v)
             out.append(lo if fn == "min" else hi if fn == "max" else (lo, hi))
         return out
 

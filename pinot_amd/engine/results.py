@@ -166,14 +166,17 @@ def merge_intermediate(function: str, a, b):
         return a + b
     if function == "sum":
         return a + b
+    # MIN / MAX merge by comparison, `a` the running result (MinAggregationFunction.merge :248-251: r1 < r2 ? r1 : r2):
+    # merge(NaN, x) = x, merge(x, NaN) = NaN, and of two zeros b. MINMAXRANGE is a.apply(b) (MinMaxRangePair.apply
+    # :51-58): an end of a is replaced only when b's compares beyond it.
     if function == "min":
-        return min(a, b)
+        return a if a < b else b
     if function == "max":
-        return max(a, b)
+        return a if a > b else b
     if function == "avg":
         return (a[0] + b[0], a[1] + b[1])
     if function == "minmaxrange":
-        return (min(a[0], b[0]), max(a[1], b[1]))
+        return (b[0] if b[0] < a[0] else a[0], b[1] if b[1] > a[1] else a[1])
     if function in ("distinctcounthll", "distinctcountrawhll"):
         return np.maximum(a, b)
     if function == "distinctcount":  # value sets (BaseDistinctAggregateAggregationFunction.merge: addAll)

@@ -10,8 +10,9 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ..segment.creator import ImmutableSegment
+from ..segment.creator import ImmutableSegment, read_chunk_forward
 from ..segment.dictionary import Dictionary
+from ..spi import DataType
 
 
 class GpuSegment:
@@ -23,6 +24,7 @@ class GpuSegment:
         self._dicts = {}
         self._sorted = {}
         self._inv_offsets = {}
+        self._specials = {}  # column -> (holds NaN, holds an infinity): real_specials
         cols = list(segment.columns.values())
         descs = (_lib.ColumnDesc * max(len(cols), 1))()
         keep = []
@@ -91,6 +93,28 @@ class GpuSegment:
             d = Dictionary(ci.dictionary, m.data_type, m.cardinality, m.string_width)
             self._dicts[column] = d
         return d
+
+    def real_specials(self, column):
+        """(holds NaN, holds an infinity) of a FLOAT / DOUBLE column, from what the segment knows without a scan of
+        the docs where it can: a sorted dictionary keeps NaN last (Double.compare order) and the infinities at its
+        ends; a raw column's chunks are read once, when a plan first asks, and the flags kept. (False, False) for
+        the other types."""
+        flags = self._specials.get(column)
+        if flags is None:
+            m = self.column_metadata(column)
+            if m.data_type not in (DataType.FLOAT, DataType.DOUBLE) or getattr(m, "hll_log2m", 0):
+                flags = (False, False)
+            else:
+                if m.has_dictionary:
+                    v = self.dictionary(column).values
+                    nan = bool(len(v)) and bool(np.isnan(v[-1]))
+                    ends = v[[0, len(v) - 1 - nan]] if len(v) > nan else v[:0]
+                else:
+                    ends = v = read_chunk_forward(self.segment.columns[column].forward, m.data_type, self.num_docs)
+                    nan = bool(np.isnan(v).any())
+                flags = (nan, bool(np.isinf(ends).any()))
+            self._specials[column] = flags
+        return flags
 
     def inverted_bytes(self, column, dict_ids) -> int:
         """Bytes of the inverted-index bitmaps of `dict_ids` (the bytes an inverted leaf reads)."""

@@ -221,6 +221,41 @@ def _chunk_forward(values: np.ndarray, dt: DataType, docs_per_chunk: int = 1000,
     return header + offs + b"".join(chunks)
 
 
+def _decompress_chunk(body: bytes, codec: int, size: int) -> bytes:
+    """The inverse of _compress_chunk: ``size`` decoded bytes."""
+    import pyarrow as pa
+    if codec == 0:
+        return body[:size]
+    if codec == 1:
+        return pa.decompress(body, decompressed_size=size, codec="snappy", asbytes=True)
+    if codec in (3, 4):
+        return pa.decompress(body[4:] if codec == 4 else body, decompressed_size=size, codec="lz4_raw", asbytes=True)
+    if codec == 2:
+        return pa.Codec("zstd").decompress(body, decompressed_size=size, asbytes=True)
+    if codec == 5:
+        import zlib
+        return zlib.decompress(body[:-4])
+    raise NotImplementedError(f"chunk compression {codec}")
+
+
+def read_chunk_forward(buf: bytes, dt: DataType, num_docs: int) -> np.ndarray:
+    """Host-side read of a fixed-byte chunk forward index (the layout _chunk_forward writes; a version-1 file has a
+    4-int header and SNAPPY chunks, BaseChunkForwardIndexReader.java:86-95): the column's values in doc order, bits
+    kept."""
+    version, num_chunks, per_chunk, entry = (int(x) for x in np.frombuffer(buf, dtype=">i4", count=4))
+    if version > 1:
+        _, codec, data_hdr = (int(x) for x in np.frombuffer(buf, dtype=">i4", count=3, offset=16))
+    else:
+        codec, data_hdr = 1, 16
+    offs = np.frombuffer(buf, dtype=">i4" if version <= 2 else ">i8", count=num_chunks, offset=data_hdr).tolist()
+    offs.append(len(buf))
+    parts = []
+    for c in range(num_chunks):
+        size = min(per_chunk, num_docs - c * per_chunk) * entry
+        parts.append(_decompress_chunk(bytes(buf[offs[c]:offs[c + 1]]), codec, size))
+    return np.frombuffer(b"".join(parts), dtype=dt.numpy_be, count=num_docs).astype(dt.numpy)
+
+
 def _var_byte_forward(values, docs_per_chunk: int = 1000, version: int = 3, compression: str = "PASS_THROUGH") -> bytes:
     """Var-byte chunk forward index of a raw STRING column (VarByteChunkForwardIndexWriter.java:37-158 over the
     BaseChunkForwardIndexWriter header): the 7-int header with lengthOfLongestEntry as the entry size, the chunk
