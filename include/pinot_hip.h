@@ -315,7 +315,7 @@ typedef struct phip_result {
   int32_t fused;              /* 1 when the filter kernel aggregated its own tiles (one launch: filter_kernel_ms and
                                  filter_bytes then cover both, agg_* are 0) */
   /* long_exact[a] = 1 when long_values[g*num_aggregations + a] holds the exact integer result (COUNT, and SUM
-   * over INT/LONG inputs whose bound sum |value| stays below 2^62); 0 when the SUM accumulated in double like
+   * over INT/LONG inputs whose bound sum |value| stays below 2^58); 0 when the SUM accumulated in double like
    * SumAggregationFunction (a possible int64 overflow) -- values[] is then the only result. */
   const int32_t *long_exact;
   /* Per-kernel device time and algorithmic bytes (the roofline numerators):
@@ -531,5 +531,22 @@ PHIP_API int32_t phip_plan_abandon_partial(uint64_t plan);
 #define PHIP_EXCHANGE_HASH 4    /* ... inserted the other sub-plans' hash-table groups into the root's table on the root device */
 /* Devices (sub-plans) of a plan and the exchange its last execution used (PHIP_EXCHANGE_*; NONE before the first). */
 PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *out_kind);
+
+/* The launch shape of a single-device plan's last execution (all 0 before the first), for tests that must know how
+ * many tiles and segments one wave walked: out_shape[i], i < num_values, in the order below. The grids follow the
+ * device's CU count, or PHIP_GRID_CUS=n (environment, n >= 1, read at plan creation) in its place: every tile-walking
+ * launch (filter, aggregation, distinct, selection, numGroupsLimit pass) and every buffer sized from its grid then
+ * follow n CUs, while the choice of kernel variant and walk keeps following the device. A node plan returns
+ * PHIP_ERR_INVALID. */
+#define PHIP_SHAPE_TOTAL_WORK 0     /* 2048-doc work tiles of the query */
+#define PHIP_SHAPE_FILTER_BLOCKS 1  /* workgroups of the filter launch (4 waves each) */
+#define PHIP_SHAPE_AGG_BLOCKS 2     /* workgroups of the aggregation launch */
+#define PHIP_SHAPE_AGG_WAVES 3      /* waves per aggregation workgroup (8 or 16) */
+#define PHIP_SHAPE_NBUF 4           /* LDS-DMA ring slots per filter wave */
+#define PHIP_SHAPE_WORK_SEGMENTS 5  /* entries of the work list (segments x programs the planner kept) */
+#define PHIP_SHAPE_DISTINCT_BLOCKS 6 /* upper bound of the distinct pass's workgroups (4 waves each) */
+#define PHIP_SHAPE_SELECT_BLOCKS 7  /* upper bound of the selection passes' workgroups (4 waves each) */
+#define PHIP_LAUNCH_SHAPE_VALUES 8
+PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values);
 
 #endif /* PINOT_HIP_H_ */

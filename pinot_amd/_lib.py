@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "phip_plan_destroy", "phip_global_dictionary", "phip_plan_execute_partial", "phip_plan_finish",
     "phip_runtime_versions", "phip_plan_abandon_partial", "phip_result_select_dictionary",
     "phip_plan_set_deadline", "phip_plan_cancel", "phip_plan_exchange", "phip_result_distinct_dictionary",
+    "phip_plan_launch_shape",
 )
 
 # phip_plan_exchange kinds (include/pinot_hip.h "node plans")
@@ -49,6 +50,10 @@ EXCHANGE_RCCL = 1
 EXCHANGE_PEER = 2
 EXCHANGE_RECORDS = 3
 EXCHANGE_HASH = 4
+
+# phip_plan_launch_shape values, in order (include/pinot_hip.h PHIP_SHAPE_*)
+LAUNCH_SHAPE_FIELDS = ("total_work", "filter_blocks", "agg_blocks", "agg_waves", "nbuf", "num_work_segments",
+                       "distinct_blocks", "select_blocks")
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 
@@ -248,6 +253,8 @@ def load(with_torch: bool = False):
     lib.phip_plan_destroy.restype = i32
     lib.phip_plan_exchange.argtypes = [u64, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.phip_plan_exchange.restype = i32
+    lib.phip_plan_launch_shape.argtypes = [u64, ctypes.POINTER(i32), i32]
+    lib.phip_plan_launch_shape.restype = i32
     lib.phip_global_dictionary.argtypes = [i32, ctypes.c_char_p, i32, i32, i32, ctypes.c_void_p]
     lib.phip_global_dictionary.restype = i32
     lib.phip_plan_execute_partial.argtypes = [u64, ctypes.POINTER(Partial)]

@@ -90,6 +90,12 @@ hipError_t launch_select_str_bytes(const uint64_t *loc, int64_t rows, const uint
                                    const uint64_t *const *offs, const uint64_t *dst_off, uint8_t *dst, hipStream_t s);
 hipError_t launch_select_gather(const DevSelQuery *q, int64_t total_work, uint64_t *out, int64_t num_rows,
                                 hipStream_t s);
+// ... on at most max_blocks workgroups (PHIP_GRID_CUS). Weak: the host simulation's stub library has only the two
+// above, and a capped plan then takes them.
+__attribute__((weak)) hipError_t launch_select_count_capped(const DevSelQuery *q, int64_t total_work, int max_blocks,
+                                                            int64_t *tile_cnt, hipStream_t s);
+__attribute__((weak)) hipError_t launch_select_gather_capped(const DevSelQuery *q, int64_t total_work, int max_blocks,
+                                                             uint64_t *out, int64_t num_rows, hipStream_t s);
 // distinct.hip (exact DISTINCTCOUNT). Weak: a build of the host code without that file (the host simulation's stub
 // library) links, and a plan that holds a PHIP_AGG_DISTINCT is refused at creation ("distinct pass not built").
 __attribute__((weak)) hipError_t launch_distinct_mark(const DevDistinctQuery *q, int64_t total_work, int lds,
@@ -2124,6 +2130,10 @@ struct Plan {
   void *dist_bits = nullptr;
   size_t dist_bytes = 0, dist_lds_bytes = 0;
   int dist_blocks = 1;
+  int sel_max_blocks = 4096;  // the selection passes' grid cap (select.hip sel_blocks; PHIP_GRID_CUS lowers it)
+  // what the last execution launched with (phip_plan_launch_shape): total_work, filter / aggregation workgroups,
+  // waves per aggregation workgroup, filter ring slots, work-list segments, distinct / selection workgroup caps
+  int32_t shape[8] = {};
   hipEvent_t dist_ev[2] = {};  // around the pass (clear + mark kernel): phip_result.distinct_kernel_ms
   // record ev[0] / ev[3] around the whole sequence (phip_result.device_ms): off by default -- every timing marker is a
   // barrier packet the command processor waits on (~4 us each, r04 host A/B); PHIP_TOTAL_EVENTS=1 records them
@@ -3838,6 +3848,16 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // each wave the deepest ring that then fits the 160 KiB LDS (bytes in flight per CU =
   // blocks x 4 waves x (nbuf-1) x slot)
   int nbuf = 0, fbpc = 0;
+  // PHIP_GRID_CUS=n (n >= 1; tests): the CU count every tile-walking launch sizes its grid from, so that a small
+  // input runs the walks with few, long-lived waves (many tiles and segment changes per wave, as at production
+  // sizes). Which kernel variant or walk runs keeps following the device's CU count.
+  int grid_cus = dev->num_cus;
+  if (const char *gc = getenv("PHIP_GRID_CUS")) {
+    if (atoi(gc) >= 1) {
+      grid_cus = atoi(gc);
+      P.sel_max_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * 8);  // (8 workgroups per CU, as the XCD walks' floor)
+    }
+  }
   const int32_t fring_bytes = fused_gb ? 4 * kFusedRingGB : (any_defer ? 4 * kFusedRingDefer : 2 * kFusedRingTile);  // per wave
   {
     const char *env = getenv("PHIP_FILTER_BPC");  // measurement override
@@ -3847,11 +3867,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     // tiles): 6 -> 3 workgroups per CU, filter 0.074 -> 0.065 ms; the unsorted layout (293K tiles, 48 per wave)
     // and small queries (every wave one or two tiles: latency) keep the default (tools/ab_env.sh, bpc A/B).
     const int64_t kMinTilesPerWave = 12;
-    const int64_t waves_at = (int64_t)dev->num_cus * want * kFilterWaves;
+    const int64_t waves_at = (int64_t)grid_cus * want * kFilterWaves;
     // (a fused launch keeps the full width: its waves also wait on gathers -- sorted Q1.1 fused 0.201 -> 0.187 ms at
     // 6 instead of 3 workgroups per CU, profiles/r03p_fused_bpc_ab.log)
     if (!env && total_work >= 4 * waves_at && !fused_any)
-      while (want > 2 && total_work < kMinTilesPerWave * (int64_t)dev->num_cus * want * kFilterWaves) want--;
+      while (want > 2 && total_work < kMinTilesPerWave * (int64_t)grid_cus * want * kFilterWaves) want--;
     const int64_t fring = (fused_any ? (int64_t)kFilterWaves * fring_bytes : 0) + gb_lds_bytes;  // fused doc rings (+ table)
     for (int bpc = want; bpc >= 1 && nbuf < 2; bpc--) {
       // a workgroup's share of the CU's 160 KiB, less 256 B for the kernel's static LDS (block partials)
@@ -3885,7 +3905,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   if (walk_env) xcd_walk = !strcmp(walk_env, "xcd") ? 1 : (!strcmp(walk_env, "xcdc") ? 2 : 0);
   int64_t min_tiles_per_wave = 1;
   if (const char *mt = getenv("PHIP_FILTER_MIN_TILES")) min_tiles_per_wave = std::max(1, atoi(mt));  // A/B
-  int filter_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)dev->num_cus * fbpc,
+  int filter_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)grid_cus * fbpc,
                                                                   ceil_div(total_work, kFilterWaves * min_tiles_per_wave)));
   if (xcd_walk) filter_blocks = (int)round_up(std::max(filter_blocks, 8), 8);
 
@@ -3959,7 +3979,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
           w.lds = lds16;
           bpc = bpc16;
         }
-        w.blocks = (int)std::min<int64_t>((int64_t)dev->num_cus * bpc, ceil_div(total_work, w.waves));
+        w.blocks = (int)std::min<int64_t>((int64_t)grid_cus * bpc, ceil_div(total_work, w.waves));
         w.blocks = (int)round_up(std::max(w.blocks, 8), 8);  // the XCD walk needs a multiple of 8 workgroups
         w.ok = w.lds <= (size_t)159 * 1024;
         return w;
@@ -3969,7 +3989,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       const Plan::GbWalk &w = P.walk[batched ? 1 : 0];
       agg_lds = w.lds;
       dq.wg_waves = w.waves;
-      agg_bpc = std::max(1, (int)((w.blocks + dev->num_cus - 1) / dev->num_cus));
+      agg_bpc = std::max(1, (int)((w.blocks + grid_cus - 1) / grid_cus));
       // Which walk runs follows the matched docs (the one-chunk walk for sparse matches, the batched one above
       // kWalkBatchDocsPerCu per CU): the plan starts with the rule above and re-chooses after every execution.
       // Measured (profiles/r06l_waves_ab.log, SSB SF100 sorted): Q3.1 21.9M docs 0.61 -> 0.47 ms batched, Q2.1 4.7M
@@ -3991,7 +4011,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     dq.rec_on = 0;
     for (DevSeg &d : dsegs) d.rec = nullptr;
   }
-  int agg_blocks = (int)std::min<int64_t>((int64_t)dev->num_cus * agg_bpc, ceil_div(total_work, dq.wg_waves));
+  int agg_blocks = (int)std::min<int64_t>((int64_t)grid_cus * agg_bpc, ceil_div(total_work, dq.wg_waves));
   agg_blocks = (int)round_up(std::max(agg_blocks, 8), 8);  // the XCD walk needs a multiple of 8 workgroups
   if (P.walk_cur >= 0) agg_blocks = P.walk[P.walk_cur].blocks;
 
@@ -4131,7 +4151,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     P.dstq_off = dstq_off;
     P.dist_lds_bytes = dstq.lds ? (size_t)round_up(std::max<int64_t>(dstq.row_words, 1) * 4, 16) : 0;
     // the LDS regime flushes once per workgroup: no more workgroups than stay resident; the global one spreads wider
-    P.dist_blocks = dev->num_cus * (dstq.lds ? 4 : 8);
+    P.dist_blocks = grid_cus * (dstq.lds ? 4 : 8);
     for (auto &e : P.dist_ev) HIP_TRY(hipEventCreate(&e));
   }
   if (nsel > 0) {
@@ -4721,7 +4741,10 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     HIP_TRY(launch_select_scan(nullptr, &tb, nullptr, nullptr, tw + 1, st));
     void *tmp;
     if ((rc = ws.get("sel_scan", std::max<size_t>(tb, 16), &tmp))) return rc;
-    HIP_TRY(launch_select_count(dsq, tw, P.sel_tile_cnt, st));
+    if (P.sel_max_blocks < 4096 && launch_select_count_capped)
+      HIP_TRY(launch_select_count_capped(dsq, tw, P.sel_max_blocks, P.sel_tile_cnt, st));
+    else
+      HIP_TRY(launch_select_count(dsq, tw, P.sel_tile_cnt, st));
     HIP_TRY(launch_select_scan(tmp, &tb, P.sel_tile_cnt, P.sel_tile_off, tw + 1, st));
     HIP_TRY(launch_select_bases(dsq, P.sel_base, P.sel_kept, P.sel_total, st));
     HIP_TRY(hipMemcpyAsync(tot, P.sel_total, 16, hipMemcpyDeviceToHost, st));
@@ -4734,7 +4757,10 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     void *out;
     if ((rc = ws.get("sel_out", (size_t)rows * P.nsel * 8, &out))) return rc;
     HIP_TRY(hipEventRecord(P.ev[4], st));
-    HIP_TRY(launch_select_gather(dsq, tw, (uint64_t *)out, rows, st));
+    if (P.sel_max_blocks < 4096 && launch_select_gather_capped)
+      HIP_TRY(launch_select_gather_capped(dsq, tw, P.sel_max_blocks, (uint64_t *)out, rows, st));
+    else
+      HIP_TRY(launch_select_gather(dsq, tw, (uint64_t *)out, rows, st));
     HIP_TRY(hipEventRecord(P.ev[2], st));
     HIP_TRY(hipMemcpyAsync(impl.sel_values.data(), out, (size_t)rows * P.nsel * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4894,6 +4920,11 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
       P.graph_failed = true;
       (void)hipGetLastError();
     }
+  }
+  if (mode != EXEC_FINISH) {
+    const int32_t sh[8] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves, P.fq.nbuf,
+                           (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks};
+    memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {
     HIP_TRY(hipGraphLaunch(P.graph_exec, st));
@@ -5983,6 +6014,17 @@ PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *
   if (rc) return rc;
   *out_parts = 1;
   *out_kind = PHIP_EXCHANGE_NONE;
+  return PHIP_OK;
+}
+
+PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values) {
+  if (!out_shape || num_values < 0) return fail(PHIP_ERR_INVALID, "null argument");
+  if (is_node_plan(plan)) return fail(PHIP_ERR_INVALID, "a node plan has one launch shape per device");
+  Plan *p;
+  int32_t rc = find_plan(plan, &p);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> xl(p->exec_mu);
+  for (int i = 0; i < num_values; i++) out_shape[i] = i < PHIP_LAUNCH_SHAPE_VALUES ? p->shape[i] : 0;
   return PHIP_OK;
 }
 

@@ -734,6 +734,17 @@ class GpuCombineOperator:
         _lib.check(_lib.load().phip_plan_exchange(self._plan, ctypes.byref(parts), ctypes.byref(kind)))
         return parts.value, kind.value
 
+    def launch_shape(self):
+        """The launch shape of the plan's last execution (phip_plan_launch_shape) as a dict of
+        _lib.LAUNCH_SHAPE_FIELDS: work tiles, filter / aggregation workgroups, waves per aggregation workgroup, filter
+        ring slots, work-list segments and the distinct / selection grid caps; None before the plan exists."""
+        if getattr(self, "_plan", None) is None:
+            return None
+        n = len(_lib.LAUNCH_SHAPE_FIELDS)
+        out = (ctypes.c_int32 * n)()
+        _lib.check(_lib.load().phip_plan_launch_shape(self._plan, out, n))
+        return dict(zip(_lib.LAUNCH_SHAPE_FIELDS, (int(v) for v in out)))
+
     def close(self):
         """Release the prepared plan (and with it the last references to unloaded segments)."""
         if getattr(self, "_plan", None):
