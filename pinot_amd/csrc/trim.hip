@@ -4,20 +4,28 @@
 // trimSize = GroupByUtils.getTableCapacity(limit, minServerGroupTrimSize) = max(5 * limit, 5000) records
 // (GroupByUtils.java:55-58,96-140; IndexedTable.finish -> TableResizer.getTopRecords). Here the compacted
 // groups are ordered on the device by a 64-bit order-preserving image of the ORDER BY aggregation
-// (Double.compare order: -0.0 < 0.0, NaN last), radix-sorted as (key, group index) pairs -- a stable sort,
-// so ties at the trim boundary keep the lowest group index -- and only the first trimSize groups are
-// gathered and copied to the host.
+// (double_order: Double.compare order, the comparator of the reference's final results, TableResizer.java:90-96 --
+// -0.0 < 0.0, and every NaN, whatever its sign bit or payload, one value above +inf), radix-sorted as
+// (key, group index) pairs -- a stable sort, so ties at the trim boundary keep the lowest group index -- and only
+// the first trimSize groups are gathered and copied to the host.
 #include <hipcub/hipcub.hpp>
 
 #include "dev_common.h"
 
 namespace phip {
 
+// The 64-bit order-preserving image of a double under Double.compare: the doubleToLongBits image (NaN canonical: a
+// SUM over a column holding 0xFFF8... carries the operand's sign bit, and the raw bits would put it below -inf),
+// negatives complemented, the others with the sign bit set.
+__device__ __forceinline__ uint64_t double_order(double d) {
+  const uint64_t u = d != d ? 0x7FF8000000000000ull : (uint64_t)__double_as_longlong(d);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
 __global__ void order_keys_kernel(const double *__restrict__ vals, int64_t n, int32_t naggs, int32_t agg, int32_t desc,
                                   uint64_t *__restrict__ ukeys, int32_t *__restrict__ idx) {
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t u = (uint64_t)__double_as_longlong(vals[g * naggs + agg]);
-    u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    const uint64_t u = double_order(vals[g * naggs + agg]);
     ukeys[g] = desc ? ~u : u;
     idx[g] = (int32_t)g;
   }
@@ -61,11 +69,6 @@ __global__ void key_order_kernel(const int64_t *__restrict__ keys, int64_t n, Ke
 
 // One radix pass of the general ORDER BY: the 64-bit order-preserving key of term j for every group, in the
 // order the previous (less significant) pass left them (perm == nullptr: group order).
-__device__ __forceinline__ uint64_t double_order(double d) {
-  const uint64_t u = (uint64_t)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // Double.compare order: -0.0 < 0.0, NaN last
-}
-
 // clearspring HyperLogLog.cardinality() (stream-lib 2.9.8, DistinctCountHLLAggregationFunction.extractFinalResult;
 // engine/reduce.py hll_cardinality): alpha * m^2 / sum 2^-reg, linear counting below 2.5 m (Long.MAX_VALUE when no
 // register is zero), rounded half up. The sum of dyadic terms is exact in any order.

@@ -8,6 +8,7 @@ BaseQueriesTest.getBrokerResponse (pinot-core/src/test/java/org/apache/pinot/que
 the server response is reduced as if it came from an OFFLINE and a REALTIME server.
 """
 import math
+import struct
 from dataclasses import dataclass, field
 from typing import List
 
@@ -43,15 +44,32 @@ def hll_cardinality(regs: np.ndarray) -> int:
     return int(math.floor(est + 0.5))
 
 
+def double_order(v: float) -> int:
+    """An order-preserving integer image of a double under Double.compare (the comparator of the reference's final
+    results, TableResizer.java:90-96): -0.0 below 0.0, every NaN -- whatever its sign bit or payload -- one value above
+    +inf. The same image orders the device trim (trim.hip double_order)."""
+    if v != v:
+        u = 0x7FF8000000000000
+    else:
+        u = struct.unpack("<Q", struct.pack("<d", v))[0]
+    return (~u & 0xFFFFFFFFFFFFFFFF) if u >> 63 else (u | 0x8000000000000000)
+
+
+def order_value(v):
+    """A final result or group-key value as Python orders it like Comparable.compareTo: a float by double_order."""
+    return double_order(float(v)) if isinstance(v, (float, np.floating)) else v
+
+
 def order_key(ob, value):
     """Sort key of one ORDER BY expression over records (used with reverse = DESC): a null (None) value -- a null
     group key or a null aggregation result under enableNullHandling -- goes last or first as ob.is_nulls_last says
-    (OrderByExpressionContext.isNullsLast; the comparator of TableResizer / the broker's reduce)."""
+    (OrderByExpressionContext.isNullsLast; the comparator of TableResizer / the broker's reduce). Floats order by
+    Double.compare (order_value): a Python float key would leave a NaN unordered and tie the two zeros."""
     high = ob.is_nulls_last != (not ob.ascending)  # where nulls sit before the DESC reversal
 
     def key(rec):
         v = value(rec)
-        return ((v is None) if high else (v is not None), v)
+        return ((v is None) if high else (v is not None), order_value(v))
     return key
 
 
@@ -208,7 +226,7 @@ def trim_groups(query: QueryContext, block, min_trim=None):
         return block
     gb_index = {str(e): i for i, e in enumerate(query.group_by)}
     recs = [(key, [final_result(a.function, x) for a, x in zip(query.aggregations, v)]) for key, v in block.groups.items()]
-    recs.sort(key=lambda r: tuple((x is None, x) for x in r[0]))  # (a null key after the values)
+    recs.sort(key=lambda r: tuple((x is None, order_value(x)) for x in r[0]))  # (a null key after the values)
 
     def value_of(expr, rec):
         if str(expr) in gb_index:

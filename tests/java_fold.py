@@ -14,8 +14,16 @@ tests/test_gpu_special_doubles.py come from these folds alone, applied to the ma
   merge_min / merge_max        MinAggregationFunction.merge (:248-251): ``r1 < r2 ? r1 : r2`` (MAX: ``>``)
   merge_minmaxrange            MinMaxRangeAggregationFunction.merge (:191): r1.apply(r2)
   seq_sum / avg                SumAggregationFunction / AvgAggregationFunction: a sequential double sum from 0.0
+
+and the order of final results (tests/test_order_by_specials.py, tests/test_gpu_order_by_specials.py):
+
+  double_compare               Double.compare: -0.0 < 0.0, every NaN equal to every other and greater than +inf
+  record_compare / top_records TableResizer's comparator (:90-96, Comparator.naturalOrder() over extractFinalResult,
+                               reversed for DESC) and the records a trim to k must / may keep under it
 """
+import functools
 import math
+import struct
 
 INF = float("inf")
 
@@ -132,3 +140,55 @@ def tree_sum(values):
             nxt.append(level[-1])
         level = nxt
     return level[0]
+
+
+def double_to_long_bits(x):
+    """Double.doubleToLongBits: the bits as a signed long, every NaN the canonical 0x7ff8000000000000."""
+    if x != x:
+        return 0x7FF8000000000000
+    return struct.unpack("<q", struct.pack("<d", x))[0]
+
+
+def double_compare(a, b):
+    """Double.compare(a, b): ``<`` / ``>`` first, then the doubleToLongBits images (-0.0 below 0.0; NaN, whatever its
+    sign bit or payload, equal to NaN and above +inf)."""
+    a, b = float(a), float(b)
+    if a < b:
+        return -1
+    if a > b:
+        return 1
+    x, y = double_to_long_bits(a), double_to_long_bits(b)
+    return 0 if x == y else (-1 if x < y else 1)
+
+
+def value_compare(a, b):
+    """Comparable.compareTo of two final results of one ORDER BY term: Long.compare for two ints (COUNT, the HLL
+    estimate, a key's position), Double.compare otherwise."""
+    if isinstance(a, int) and isinstance(b, int):
+        return (a > b) - (a < b)
+    return double_compare(a, b)
+
+
+def record_compare(terms):
+    """TableResizer's comparator over ``terms`` = [(value, ascending)], ``value`` a function of a record returning
+    the term's final result (a float, an int, or a key's position as an int): the first term that does not tie
+    decides, DESC reversed. Returns cmp(r1, r2)."""
+    def cmp(r1, r2):
+        for value, ascending in terms:
+            c = value_compare(value(r1), value(r2))
+            if c:
+                return c if ascending else -c
+        return 0
+    return cmp
+
+
+def top_records(records, terms, k):
+    """(must_keep, may_keep) of a trim of ``records`` to its first ``k`` by record_compare(terms): the records strictly
+    before the k-th record's equivalence class, and that class (whose members the reference picks by heap order).
+    Without ties may_keep fills exactly the remaining places."""
+    cmp = record_compare(terms)
+    ordered = sorted(records, key=functools.cmp_to_key(cmp))
+    if k >= len(ordered):
+        return ordered, []
+    pivot = ordered[k - 1]
+    return [r for r in ordered if cmp(r, pivot) < 0], [r for r in ordered if cmp(r, pivot) == 0]
