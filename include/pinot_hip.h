@@ -546,7 +546,8 @@ PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *
 #define PHIP_SHAPE_WORK_SEGMENTS 5  /* entries of the work list (segments x programs the planner kept) */
 #define PHIP_SHAPE_DISTINCT_BLOCKS 6 /* upper bound of the distinct pass's workgroups (4 waves each) */
 #define PHIP_SHAPE_SELECT_BLOCKS 7  /* upper bound of the selection passes' workgroups (4 waves each) */
-#define PHIP_LAUNCH_SHAPE_VALUES 8
+#define PHIP_SHAPE_FUSED_LEAN 8     /* 1: the filter launch was the lean fused instantiation (bit-sliced + deferred) */
+#define PHIP_LAUNCH_SHAPE_VALUES 9
 PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values);
 
 #endif /* PINOT_HIP_H_ */

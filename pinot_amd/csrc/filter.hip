@@ -115,12 +115,15 @@ hipError_t launch_roaring_or(const RoaringTask *tasks, const RoaringGroup *group
 }
 
 
-// the eight filter_kernel instantiations, one translation unit each (filter_k*.hip)
+// the eleven filter_kernel instantiations, one translation unit each (filter_k*.hip)
 hipError_t launch_filter_general(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_conj(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_fused1(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_fused2(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_fused4(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
+hipError_t launch_filter_lean1(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
+hipError_t launch_filter_lean2(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
+hipError_t launch_filter_lean4(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_fusedgb(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_fusedgbx(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 hipError_t launch_filter_fusedgbl(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
@@ -140,6 +143,17 @@ hipError_t launch_filter(const DevFilter &q, bool conj_only, int fused_naggs, in
   if (fused_naggs <= 1) return launch_filter_fused1(q, nblocks, lds_bytes, s, e0, e1);
   if (fused_naggs <= 2) return launch_filter_fused2(q, nblocks, lds_bytes, s, e0, e1);
   return launch_filter_fused4(q, nblocks, lds_bytes, s, e0, e1);
+}
+
+// The lean shape of a fused aggregation (filter_kernel.h kBsDefer; fused_naggs > 0): every segment's program is the
+// bit-sliced conjunction and every segment defers its projection -- the host decides (runtime.cpp fused_lean). Its own
+// entry point, not an argument of launch_filter: a build of the host code without it keeps linking and takes the
+// general instantiation (runtime.cpp declares it weak, as the capped selection launches).
+hipError_t launch_filter_lean(const DevFilter &q, int fused_naggs, int nblocks, size_t lds_bytes, hipStream_t s,
+                              hipEvent_t e0, hipEvent_t e1) {
+  if (fused_naggs <= 1) return launch_filter_lean1(q, nblocks, lds_bytes, s, e0, e1);
+  if (fused_naggs <= 2) return launch_filter_lean2(q, nblocks, lds_bytes, s, e0, e1);
+  return launch_filter_lean4(q, nblocks, lds_bytes, s, e0, e1);
 }
 
 hipError_t launch_masks_to_words(const uint32_t *masks, int32_t tile0, int32_t ntiles, uint64_t *words, int64_t nwords,

@@ -1131,6 +1131,9 @@ struct TileRank {
   int32_t step;
   int total;
 };
+// (a constant, not the caller's batch: the order in which a tile's docs enter the ring, and with it the grouping of a
+// floating-point sum, must not depend on the batch a kernel variant gathers with)
+constexpr int kRankContigMin = 256;
 __device__ __forceinline__ TileRank rank_tile(uint32_t mask) {
   const int lane = lane_id();
   TileRank r;
@@ -1140,7 +1143,7 @@ __device__ __forceinline__ TileRank rank_tile(uint32_t mask) {
   r.total = __builtin_amdgcn_readlane((int)r.incl, 63);
   r.base = lane;
   r.step = 64;
-  if (r.total >= 64 * kFusedBatch) {
+  if (r.total >= kRankContigMin) {
     r.w = lane_major_to_contig(mask);
     cnt = (uint32_t)__popc(r.w);
     r.incl = wave_incl_scan(cnt);
@@ -1199,21 +1202,21 @@ __device__ __forceinline__ void fused_tile(cquery_t &aq, cseg_t &seg, const Tile
   }
 }
 
-// deferred mode: kFusedBatch chunks of the ring (segment docs, columns from HBM)
-template <int NA>
+// deferred mode: U chunks of the ring (segment docs, columns from HBM)
+template <int NA, int U = kFusedBatch>
 __device__ __forceinline__ void fused_flush(cquery_t &aq, cseg_t &seg, const PHIP_LDS uint32_t *ring, int tail, int n,
                                             const SmallDict (&sda)[NA], const SmallDict (&sdb)[NA], uint64_t (&acc)[NA]) {
   const int lane = lane_id();
-  int32_t d[kFusedBatch];
+  int32_t d[U];
   uint32_t act = 0;
 #pragma unroll
-  for (int u = 0; u < kFusedBatch; u++) {
+  for (int u = 0; u < U; u++) {
     const bool on = 64 * u + lane < n;
     d[u] = on ? (int32_t)ring[(tail + 64 * u + lane) & (kFusedRingDefer - 1)] : 0;
     act |= on ? (1u << u) : 0u;
   }
   const Tile tz{0, 0, nullptr};
-  fused_batch<NA, kFusedBatch, true>(aq, seg, tz, d, act, sda, sdb, acc);
+  fused_batch<NA, U, true>(aq, seg, tz, d, act, sda, sdb, acc);
 }
 
 constexpr int defer_piece_lanes(int room) {  // the largest power of two <= room / 32 lanes (at most 64)
@@ -1221,8 +1224,19 @@ constexpr int defer_piece_lanes(int room) {  // the largest power of two <= room
   while (l > 1 && l * 32 > room) l >>= 1;
   return l;
 }
-constexpr int kDeferPieceLanes = defer_piece_lanes(kFusedRingDefer - 64 * kFusedBatch);
-static_assert(kFusedRingDefer - 64 * kFusedBatch >= 32 * kDeferPieceLanes, "a piece fits the ring beside a batch");
+static_assert(kFusedRingDefer - 64 * kFusedBatch >= 32 * defer_piece_lanes(kFusedRingDefer - 64 * kFusedBatch),
+              "a piece fits the ring beside a batch");
+// The lean kernel's batch (filter_kernel kBsDefer) with one aggregation. (Measured and not kept, round 7: without the
+// general kernel's unused paths 5 and 6 chunks per gather round trip fit its registers without spills -- 89 / 96 VGPRs,
+// profiles/r07_fused_lean_resources.txt -- but sorted Q1.1 ran 0.1115 -> 0.126 / 0.125 ms and unsorted Q1.1 unchanged,
+// profiles/r07_lean_batch_ab.log: at ~290 matched docs per tile a 4-chunk batch fills about once per tile, a larger one
+// leaves docs waiting across tiles. NA = 2 / 4 spill at 5 or 6 chunks.)
+#ifndef PHIP_LEAN_BATCH
+#define PHIP_LEAN_BATCH 4  // (A/B builds override it)
+#endif
+constexpr int lean_batch(int na) { return na == 1 ? PHIP_LEAN_BATCH : kFusedBatch; }
+static_assert(kFusedRingDefer - 64 * lean_batch(1) >= 32 * defer_piece_lanes(kFusedRingDefer - 64 * lean_batch(1)),
+              "a piece fits the ring beside a lean batch");
 
 // (Measured and not kept, round 5: a 256-entry ring flushed 128 docs at a time -- 1 KiB per wave, as the fused group-by
 // uses -- sorted Q1.1 0.136 -> 0.231 ms, unsorted Q1.3 0.352 -> 0.431: half the loads in flight per wave costs more than
@@ -1235,15 +1249,16 @@ static_assert(kFusedRingDefer - 64 * kFusedBatch >= 32 * kDeferPieceLanes, "a pi
 // (Measured and not kept, round 5: dense tiles projected in place, lane-major, 8 groups per round trip -- sorted
 // Q1.1 0.180 -> 0.374 ms at >= 256 matched docs per tile: four dependent round trips per tile instead of one per
 // 256 deferred docs; profiles/r05e_dense.log.)
-template <int NA>
+template <int NA, int U = kFusedBatch>
 __device__ __forceinline__ void fused_defer(cquery_t &aq, cseg_t &seg, const Tile &t, uint32_t mask,
                                             PHIP_LDS uint32_t *ring, int &head, int &tail, const SmallDict (&sda)[NA],
                                             const SmallDict (&sdb)[NA], uint64_t (&acc)[NA]) {
+  constexpr int kDeferPieceLanes = defer_piece_lanes(kFusedRingDefer - 64 * U);
   if (ballot(mask != 0) == 0) return;
   const TileRank r = rank_tile(mask);
   const int head0 = head;
   // the whole tile when the ring has room, else pieces of kDeferPieceLanes lanes (<= 32 docs a lane) each after
-  // draining the ring below one batch (< 64 x kFusedBatch pending + the piece <= kFusedRingDefer): eighth tiles for
+  // draining the ring below one batch (< 64 x U pending + the piece <= kFusedRingDefer): eighth tiles for
   // the default 512-entry ring and 4-chunk batch
   const int npiece = head - tail + r.total <= kFusedRingDefer ? 1 : 64 / kDeferPieceLanes;
   const int lanes = 64 / npiece;
@@ -1251,9 +1266,9 @@ __device__ __forceinline__ void fused_defer(cquery_t &aq, cseg_t &seg, const Til
     const int e = __builtin_amdgcn_readlane((int)r.incl, lanes * p + lanes - 1);
     write_ranked<uint32_t, kFusedRingDefer>(r, lanes * p, lanes * (p + 1), -head0, t.doc0, ring);
     head = head0 + e;
-    while (head - tail >= 64 * kFusedBatch) {
-      fused_flush<NA>(aq, seg, ring, tail, 64 * kFusedBatch, sda, sdb, acc);
-      tail += 64 * kFusedBatch;
+    while (head - tail >= 64 * U) {
+      fused_flush<NA, U>(aq, seg, ring, tail, 64 * U, sda, sdb, acc);
+      tail += 64 * U;
     }
   }
 }
@@ -1363,9 +1378,17 @@ __device__ __forceinline__ void cursor_issue(StageCursor<kS> &c, uint32_t lbase,
 #define PHIP_FUSED_WAVES 5  // waves per SIMD the fused launches are compiled for: the LDS admits 5 workgroups (20 waves)
                             // per CU, and 6 left 68 B of spills per lane (sorted Q1.1 -5 %, profiles/r05j_ablib_waves.log)
 #endif
-template <bool kConjOnly, int NA>
+// kBsDefer: the lean shape of a fused aggregation (NA > 0) -- every segment's program is the bit-sliced conjunction
+// (eval_conj_bs; conj == 0 and the conj_range doc-range cut included) and every segment defers its projection
+// (fused_defer / fused_flush from HBM). The P-layout conjunction, the per-tile streamed projection, the tile-mask
+// store and the streamed value columns' cursor entries are compiled out: carried along unused they cost the headline
+// 16 VGPR and 149 SGPR spills (36 B of scratch per lane, profiles/r07_fused_lean_resources.txt). The host picks it
+// (runtime.cpp fused_lean); plans it does not cover keep the general instantiation.
+template <bool kConjOnly, int NA, bool kBsDefer = false>
 __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAVES : 6) : 4) void filter_kernel(DevFilter q) {
-  constexpr int kSConj = NA > 0 ? kMaxConj + kMaxAggStage : kMaxConj;
+  static_assert(!kBsDefer || (kConjOnly && NA > 0), "the lean shape is a fused aggregation");
+  // (lean: the staged sources are the conjunction's planes alone, at most one region per leaf)
+  constexpr int kSConj = kBsDefer ? kMaxConj : (NA > 0 ? kMaxConj + kMaxAggStage : kMaxConj);
   constexpr int kS = kConjOnly ? (kSConj < kMaxStage ? kSConj : kMaxStage) : kMaxStage;  // (DevSeg.stage size)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
@@ -1416,8 +1439,9 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
   // after it: >= min_dma per later prefetched tile, plus the mask stores of the tiles evaluated since
   // (atomics only add to the true count). Waiting for fewer outstanding operations is always safe.
   const int nd = q.min_dma;
-  const int st = q.mask_out != nullptr ? 1 : 0;
+  const int st = kBsDefer ? 0 : (q.mask_out != nullptr ? 1 : 0);  // (a fused aggregation stores no tile masks)
   constexpr int NAX = NA > 0 ? NA : 1;
+  constexpr int kB = kBsDefer ? lean_batch(NA) : kFusedBatch;  // chunks per deferred gather batch
   constexpr int kGbMode = NA == kFusedGroupByXcd ? GB_XCD : (NA == kFusedGroupByLds ? GB_LDS : GB_GLOBAL);
   // (NA < 0: the fused group-by's table; GB_LDS: the workgroup's, after every wave's DMA and doc rings)
   lds_u64 *gtbl = nullptr;
@@ -1473,7 +1497,7 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
     if (t >= seg_end) {  // entering a new segment: flush the previous one's count
       if constexpr (NA > 0) {  // the previous segment's deferred docs, before its small dictionaries go
         if (si >= 0 && dhead > dtail)
-          fused_flush<NA>(*(cquery_t *)q.agg, segs[si], deferring, dtail, dhead - dtail, sda, sdb, acc);
+          fused_flush<NA, kB>(*(cquery_t *)q.agg, segs[si], deferring, dtail, dhead - dtail, sda, sdb, acc);
         dhead = dtail = 0;
       }
       if constexpr (NA < 0) {  // (the group keys are the segment's: flushed before it ends)
@@ -1518,7 +1542,8 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
     if (q.probe) {
       mask = valid;
     } else if (kConjOnly || seg.conj_path) {
-      mask = seg.conj > 0 ? eval_conj(seg, tl.stage, valid) : valid;
+      if constexpr (kBsDefer) mask = seg.conj > 0 ? (valid & eval_conj_bs(seg, tl.stage)) : valid;
+      else mask = seg.conj > 0 ? eval_conj(seg, tl.stage, valid) : valid;
       if (seg.conj_range && (seg.conj_lo > tl.doc0 || seg.conj_hi < tl.doc0 + kTileDocs - 1)) {
         const int32_t lo = max(seg.conj_lo - tl.doc0, 0), hi = min(seg.conj_hi - tl.doc0, kTileDocs - 1);
         mask &= lo <= hi ? range_word(lo, hi, lane) : 0u;
@@ -1538,15 +1563,20 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
       else *mo = mask;
     }
     if constexpr (NA > 0) {
-      if (seg.fused_defer) fused_defer<NA>(*(cquery_t *)q.agg, seg, tl, mask, deferring, dhead, dtail, sda, sdb, acc);
-      else fused_tile<NA>(*(cquery_t *)q.agg, seg, tl, mask, docring, sda, sdb, acc);
+      if constexpr (kBsDefer) {
+        fused_defer<NA, kB>(*(cquery_t *)q.agg, seg, tl, mask, deferring, dhead, dtail, sda, sdb, acc);
+      } else {
+        if (seg.fused_defer) fused_defer<NA>(*(cquery_t *)q.agg, seg, tl, mask, deferring, dhead, dtail, sda, sdb, acc);
+        else fused_tile<NA>(*(cquery_t *)q.agg, seg, tl, mask, docring, sda, sdb, acc);
+      }
     }
     if constexpr (NA < 0) fused_defer_gb<kGbMode>(*(cquery_t *)q.agg, seg, tl, mask, deferring, dhead, dtail, gtbl, ghll);
     slot = slot + 1 == nbuf ? 0 : slot + 1;
   }
 #undef PHIP_PREFETCH
   if constexpr (NA > 0) {
-    if (si >= 0 && dhead > dtail) fused_flush<NA>(*(cquery_t *)q.agg, segs[si], deferring, dtail, dhead - dtail, sda, sdb, acc);
+    if (si >= 0 && dhead > dtail)
+      fused_flush<NA, kB>(*(cquery_t *)q.agg, segs[si], deferring, dtail, dhead - dtail, sda, sdb, acc);
   }
   if constexpr (NA < 0) {
     while (si >= 0 && dhead > dtail) {
@@ -1609,21 +1639,21 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
 }
 
 
-template <bool C, int NA>
+template <bool C, int NA, bool L = false>
 hipError_t launch_filter_t(const DevFilter &q, int nblocks, size_t lds_bytes, hipStream_t s, hipEvent_t e0,
                                   hipEvent_t e1) {
   if (lds_bytes > 65536) {
     // allow > 64 KiB dynamic LDS (gfx950: 160 KiB per workgroup); once, thread-safe (magic static)
-    static const hipError_t configured = hipFuncSetAttribute((const void *)filter_kernel<C, NA>,
+    static const hipError_t configured = hipFuncSetAttribute((const void *)filter_kernel<C, NA, L>,
                                                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840 - 1024);
     if (configured != hipSuccess) return configured;
   }
   if (e0 != nullptr) {  // timing carried by the dispatch packet itself (no barrier packets around it)
     void *args[] = {(void *)&q};
-    return hipExtLaunchKernel((const void *)filter_kernel<C, NA>, dim3(nblocks), dim3(kFilterBlock), args, lds_bytes, s,
+    return hipExtLaunchKernel((const void *)filter_kernel<C, NA, L>, dim3(nblocks), dim3(kFilterBlock), args, lds_bytes, s,
                               e0, e1, 0);
   }
-  filter_kernel<C, NA><<<nblocks, kFilterBlock, lds_bytes, s>>>(q);
+  filter_kernel<C, NA, L><<<nblocks, kFilterBlock, lds_bytes, s>>>(q);
   return hipGetLastError();
 }
 

@@ -55,6 +55,10 @@ hipError_t launch_xcd_merge(uint64_t *tab, int64_t words, int64_t G, const int32
 hipError_t launch_roaring_or(const RoaringTask *tasks, const RoaringGroup *groups, int32_t ngroups, hipStream_t s);
 hipError_t launch_filter(const DevFilter &q, bool conj_only, int fused_naggs, int nblocks, size_t lds_bytes,
                          hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the lean fused shape (filter.hip). Weak: the host simulation's stub library has launch_filter alone, and a plan then
+// keeps the general instantiation.
+__attribute__((weak)) hipError_t launch_filter_lean(const DevFilter &q, int fused_naggs, int nblocks, size_t lds_bytes,
+                                                    hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 hipError_t launch_masks_to_words(const uint32_t *masks, int32_t tile0, int32_t ntiles, uint64_t *words, int64_t nwords,
                                  hipStream_t s);
 hipError_t launch_agg(const DevAggQuery &q, const DevAggQuery *dq, int nblocks, size_t lds, hipStream_t s,
@@ -2057,6 +2061,7 @@ struct Plan {
   std::vector<ProjCol> proj;
   bool has_filter = false, need_agg = false, need_mask = false, group_by = false, conj_only = false;
   int fused_naggs = 0;  // > 0: the filter kernel aggregates (fused_tile), no aggregation launch
+  bool fused_lean = false;  // ... in its lean shape (filter_kernel.h kBsDefer): bit-sliced conjunctions, deferred gathers
   bool fused_gb = false;  // the filter kernel runs the dense group-by into the HBM table (no aggregation launch)
   bool gb_xcd = false;    // ... into kXcdCopies XCD-private copies of it (GB_XCD), merged after the launch
   bool gb_lds = false;    // ... into each workgroup's LDS table (GB_LDS), its slabs reduced after the launch
@@ -2133,7 +2138,7 @@ struct Plan {
   int sel_max_blocks = 4096;  // the selection passes' grid cap (select.hip sel_blocks; PHIP_GRID_CUS lowers it)
   // what the last execution launched with (phip_plan_launch_shape): total_work, filter / aggregation workgroups,
   // waves per aggregation workgroup, filter ring slots, work-list segments, distinct / selection workgroup caps
-  int32_t shape[8] = {};
+  int32_t shape[PHIP_LAUNCH_SHAPE_VALUES] = {};
   hipEvent_t dist_ev[2] = {};  // around the pass (clear + mark kernel): phip_result.distinct_kernel_ms
   // record ev[0] / ev[3] around the whole sequence (phip_result.device_ms): off by default -- every timing marker is a
   // barrier packet the command processor waits on (~4 us each, r04 host A/B); PHIP_TOTAL_EVENTS=1 records them
@@ -3844,6 +3849,16 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   const bool conj_only = conj_all;
   if (fused_naggs > 0 || fused_gb) need_mask = false;  // the filter kernel aggregates its own tiles
   const bool fused_any = fused_naggs > 0 || fused_gb;
+  // The lean fused instantiation (filter_kernel.h kBsDefer) when the whole launch has its shape: a fused aggregation
+  // whose segments all evaluate the bit-sliced conjunction (or none: conj == 0 with the doc-range cut) and all defer
+  // their projection. It compiles out the P-layout conjunction and the per-tile streamed projection, which cost the
+  // general instantiation 16 VGPR / 149 SGPR spills on the headline. Then no segment stages more than
+  // its conjunction's planes (<= kMaxConj regions, the lean cursor's size). PHIP_FUSED_LEAN=0 keeps the general
+  // instantiation (A/B).
+  bool fused_lean = fused_naggs > 0 && !fused_gb && conj_only && launch_filter_lean != nullptr;
+  for (const DevSeg &ds : dsegs)
+    fused_lean = fused_lean && (ds.conj == 0 || ds.conj_bs != 0) && ds.fused_defer == 1 && ds.num_stage <= kMaxConj;
+  if (const char *le = getenv("PHIP_FUSED_LEAN")) fused_lean = fused_lean && atoi(le) != 0;
   // ring depth: prefer 4 workgroups (16 waves) per CU for the VALU/LDS work of the leaves, and give
   // each wave the deepest ring that then fits the 160 KiB LDS (bytes in flight per CU =
   // blocks x 4 waves x (nbuf-1) x slot)
@@ -4304,6 +4319,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   P.node_part = tl_node_docs > 0;
   P.conj_only = conj_only;
   P.fused_naggs = fused_naggs;
+  P.fused_lean = fused_lean;
   P.fused_gb = fused_gb;
   P.gb_xcd = gb_xcd;
   P.gb_lds = gb_lds;
@@ -4489,7 +4505,9 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   const bool ext_events = P.timed && total_work > 0 && nkern == 1 && !P.split_event && xe && atoi(xe) != 0;
   hipEvent_t e0 = ext_events ? P.ev[1] : nullptr, e1 = ext_events ? P.ev[2] : nullptr;
   if (!ext_events && P.timed) HIP_TRY(hipEventRecord(P.ev[1], st));
-  if (has_filter && total_work > 0)
+  if (has_filter && total_work > 0 && P.fused_lean)
+    HIP_TRY(launch_filter_lean(fq, P.fused_naggs, filter_blocks, filter_lds, st, e0, e1));
+  else if (has_filter && total_work > 0)
     HIP_TRY(launch_filter(fq, conj_only, P.fused_gb ? (P.gb_lds ? -3 : (P.gb_xcd ? -2 : -1)) : P.fused_naggs, filter_blocks,
                           filter_lds, st, e0, e1));
   // (a plan of one kernel -- fused, or a filter or aggregation alone -- needs no split event)
@@ -4922,8 +4940,9 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     }
   }
   if (mode != EXEC_FINISH) {
-    const int32_t sh[8] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves, P.fq.nbuf,
-                           (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks};
+    const int32_t sh[PHIP_LAUNCH_SHAPE_VALUES] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves,
+                                                  P.fq.nbuf, (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks,
+                                                  P.fused_lean ? 1 : 0};
     memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {

@@ -25,7 +25,7 @@ HBM_PEAK_GBS = 8000.0
 
 
 def family(name):
-    m = re.search(r"phip::filter_kernel<(\w+), (-?\d+)>", name)
+    m = re.search(r"phip::filter_kernel<(\w+), (-?\d+)(?:, \w+)?>", name)
     if m:
         return "fused_filter_agg" if int(m.group(2)) != 0 else "filter_kernel"
     if "phip::agg_kernel<" in name:

@@ -21,7 +21,7 @@ import re
 def family(kernel_name):
     """filter_kernel (plain filter launch), fused_filter_agg (filter_kernel<C, NA> with NA > 0: it aggregated its
     own tiles) or agg_kernel; None for the small kernels."""
-    m = re.search(r"phip::filter_kernel<(\w+), (\d+)>", kernel_name)
+    m = re.search(r"phip::filter_kernel<(\w+), (\d+)(?:, \w+)?>", kernel_name)
     if m:
         return "fused_filter_agg" if int(m.group(2)) > 0 else "filter_kernel"
     if "phip::agg_kernel<" in kernel_name:
