@@ -19,6 +19,7 @@
 #include <hip/hip_ext.h>
 
 #include "agg_common.h"
+#include "launch.h"
 
 namespace phip {
 // Fixed-order reduction of the per-workgroup group-table slabs into the global layout
@@ -120,20 +121,6 @@ __global__ __launch_bounds__(256) void slab_reduce_wave_kernel(const uint64_t *_
 // blocks in a fixed order, then a fixed shuffle tree (bitwise reproducible run to run).
 __device__ __forceinline__ void finalize_slot(const uint64_t *__restrict__ partials, int nblocks, int nslots,
                                               const int32_t *__restrict__ kinds, uint64_t *__restrict__ out, int a);
-
-__global__ void finalize_partials_kernel(const uint64_t *__restrict__ partials, int nblocks, int nslots,
-                                         const int32_t *__restrict__ kinds, uint64_t *__restrict__ out) {
-  if ((int)blockIdx.x < nslots) finalize_slot(partials, nblocks, nslots, kinds, out, blockIdx.x);
-}
-
-// Both partial sets of a filtered aggregation in one launch (blocks [0, na) -> set a, the rest -> set b).
-__global__ void finalize_partials2_kernel(const uint64_t *__restrict__ pa, int nba, int na, const int32_t *__restrict__ ka,
-                                          uint64_t *__restrict__ oa, const uint64_t *__restrict__ pb, int nbb, int nb,
-                                          const int32_t *__restrict__ kb, uint64_t *__restrict__ ob) {
-  const int i = blockIdx.x;
-  if (i < na) finalize_slot(pa, nba, na, ka, oa, i);
-  else if (i < na + nb) finalize_slot(pb, nbb, nb, kb, ob, i - na);
-}
 
 // Every per-execution result of an aggregation query in one launch, written straight into the plan's pinned
 // host landing area (device-visible host memory; visible to the host once the stream has synchronised):
@@ -456,16 +443,6 @@ hipError_t launch_slab_reduce(const uint64_t *slab, int32_t nslabs, int32_t tbl_
   return hipGetLastError();
 }
 
-hipError_t launch_finalize_partials(const uint64_t *partials, int nblocks, int nslots, const int32_t *kinds,
-                                    uint64_t *out, hipStream_t s) {
-  finalize_partials_kernel<<<nslots, 64, 0, s>>>(partials, nblocks, nslots, kinds, out);
-  return hipGetLastError();
-}
-hipError_t launch_finalize_partials2(const uint64_t *pa, int nba, int na, const int32_t *ka, uint64_t *oa,
-                                     const uint64_t *pb, int nbb, int nb, const int32_t *kb, uint64_t *ob, hipStream_t s) {
-  finalize_partials2_kernel<<<na + nb, 64, 0, s>>>(pa, nba, na, ka, oa, pb, nbb, nb, kb, ob);
-  return hipGetLastError();
-}
 hipError_t launch_finalize_all(const uint64_t *pa, int nba, int na, const int32_t *ka, const uint64_t *pf, int nbf,
                                const int32_t *kf, uint64_t *segm, int nseg, uint32_t *hll, int hll_words, uint64_t *out,
                                hipStream_t s, uint32_t *ticket, uint64_t seq) {

@@ -96,6 +96,11 @@ enum GroupMode : int32_t {
                   // memory side), merged into copy 0 by xcd_merge_kernel; the plan's mode stays GB_GLOBAL
 };
 constexpr int kXcdCopies = 8;  // MI355X: 8 XCDs (HW_REG_XCC_ID & 7)
+// filter_kernel's NA template argument when the dense group-by runs inside the filter kernel (filter_kernel.h), by the
+// table's placement: GB_GLOBAL, GB_XCD, GB_LDS. NA >= 0 counts fused aggregations.
+constexpr int kFusedGroupBy = -1;
+constexpr int kFusedGroupByXcd = -2;
+constexpr int kFusedGroupByLds = -3;
 constexpr uint64_t kHashEmpty = ~0ull;  // empty key slot (mixed-radix keys are < 2^62)
 
 // One column as seen by one segment of a query.

@@ -20,6 +20,7 @@
 //                              rows gathered back to back (phip_result.distinct_words).
 // Integer OR is order-free, so the bitmaps are bit-reproducible whatever the schedule.
 #include "agg_common.h"
+#include "launch.h"
 
 namespace phip {
 
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(kDstBlock) void distinct_finish_kernel(const DevDis
   }
 }
 
-// ---- host-callable launchers (runtime.cpp; declared weak there: a build without this file refuses DISTINCT plans) ----
+// ---- host-callable launchers (launch.h) -------------------------------------------------------------------------
 hipError_t launch_distinct_mark(const DevDistinctQuery *q, int64_t total_work, int lds, size_t lds_bytes, int max_blocks,
                                 hipStream_t s) {
   if (total_work <= 0) return hipSuccess;

@@ -20,6 +20,7 @@
 #include <hip/hip_ext.h>
 
 #include "agg_common.h"
+#include "launch.h"
 
 namespace phip {
 // ------------------------------------------------------------------------------------------------
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void masks_to_words_kernel(const uint32_t *__r
 }
 
 // ------------------------------------------------------------------------------------------------
-// host-callable launchers (runtime.cpp)
+// host-callable launchers (launch.h)
 // ------------------------------------------------------------------------------------------------
 hipError_t launch_roaring_or(const RoaringTask *tasks, const RoaringGroup *groups, int32_t ngroups, hipStream_t s) {
   if (ngroups <= 0) return hipSuccess;
@@ -114,46 +115,29 @@ hipError_t launch_roaring_or(const RoaringTask *tasks, const RoaringGroup *group
   return hipGetLastError();
 }
 
+// filter_kernel<C, NA, L> (filter_kernel.h), explicitly instantiated one translation unit each (filter_k_*.hip)
+template <bool C, int NA, bool L = false>
+hipError_t launch_filter_t(const DevFilter &q, int nblocks, size_t lds_bytes, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 
-// the eleven filter_kernel instantiations, one translation unit each (filter_k*.hip)
-hipError_t launch_filter_general(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_conj(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_fused1(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_fused2(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_fused4(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_lean1(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_lean2(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_lean4(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_fusedgb(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_fusedgbx(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-hipError_t launch_filter_fusedgbl(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
-
-// conj_only: every segment's program takes the conjunctive fast path (the interpreter is compiled
-// out, which frees registers for more resident waves); fused_naggs > 0: the aggregation runs inside
-// (q.agg set, conj_only required); fused_naggs < 0: the dense group-by runs inside (q.agg set), -1 into the HBM
-// table, -2 into its XCD-private copies, -3 into the workgroup's LDS table
-// (e0 / e1: optional start / stop events recorded by the kernel's own dispatch, hipExtLaunchKernel)
-hipError_t launch_filter(const DevFilter &q, bool conj_only, int fused_naggs, int nblocks, size_t lds_bytes,
+hipError_t launch_filter(const DevFilter &q, FilterVariant variant, int naggs, int nblocks, size_t lds_bytes,
                          hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-  if (!conj_only) return launch_filter_general(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs == -3) return launch_filter_fusedgbl(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs == -2) return launch_filter_fusedgbx(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs < 0) return launch_filter_fusedgb(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs == 0) return launch_filter_conj(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs <= 1) return launch_filter_fused1(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs <= 2) return launch_filter_fused2(q, nblocks, lds_bytes, s, e0, e1);
-  return launch_filter_fused4(q, nblocks, lds_bytes, s, e0, e1);
-}
-
-// The lean shape of a fused aggregation (filter_kernel.h kBsDefer; fused_naggs > 0): every segment's program is the
-// bit-sliced conjunction and every segment defers its projection -- the host decides (runtime.cpp fused_lean). Its own
-// entry point, not an argument of launch_filter: a build of the host code without it keeps linking and takes the
-// general instantiation (runtime.cpp declares it weak, as the capped selection launches).
-hipError_t launch_filter_lean(const DevFilter &q, int fused_naggs, int nblocks, size_t lds_bytes, hipStream_t s,
-                              hipEvent_t e0, hipEvent_t e1) {
-  if (fused_naggs <= 1) return launch_filter_lean1(q, nblocks, lds_bytes, s, e0, e1);
-  if (fused_naggs <= 2) return launch_filter_lean2(q, nblocks, lds_bytes, s, e0, e1);
-  return launch_filter_lean4(q, nblocks, lds_bytes, s, e0, e1);
+  const int na = naggs <= 1 ? 1 : (naggs <= 2 ? 2 : 4);  // (the fused variants' accumulator count)
+  switch (variant) {
+    case FV_GENERAL: return launch_filter_t<false, 0>(q, nblocks, lds_bytes, s, e0, e1);
+    case FV_CONJ: return launch_filter_t<true, 0>(q, nblocks, lds_bytes, s, e0, e1);
+    case FV_FUSED:
+      if (na == 1) return launch_filter_t<true, 1>(q, nblocks, lds_bytes, s, e0, e1);
+      if (na == 2) return launch_filter_t<true, 2>(q, nblocks, lds_bytes, s, e0, e1);
+      return launch_filter_t<true, 4>(q, nblocks, lds_bytes, s, e0, e1);
+    case FV_FUSED_LEAN:
+      if (na == 1) return launch_filter_t<true, 1, true>(q, nblocks, lds_bytes, s, e0, e1);
+      if (na == 2) return launch_filter_t<true, 2, true>(q, nblocks, lds_bytes, s, e0, e1);
+      return launch_filter_t<true, 4, true>(q, nblocks, lds_bytes, s, e0, e1);
+    case FV_GB: return launch_filter_t<true, kFusedGroupBy>(q, nblocks, lds_bytes, s, e0, e1);
+    case FV_GB_XCD: return launch_filter_t<true, kFusedGroupByXcd>(q, nblocks, lds_bytes, s, e0, e1);
+    case FV_GB_LDS: return launch_filter_t<true, kFusedGroupByLds>(q, nblocks, lds_bytes, s, e0, e1);
+  }
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_masks_to_words(const uint32_t *masks, int32_t tile0, int32_t ntiles, uint64_t *words, int64_t nwords,

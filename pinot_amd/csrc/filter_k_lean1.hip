@@ -2,8 +2,5 @@
 #include "filter_kernel.h"
 
 namespace phip {
-hipError_t launch_filter_lean1(const DevFilter &q, int nblocks, size_t lds_bytes, hipStream_t s, hipEvent_t e0,
-                              hipEvent_t e1) {
-  return launch_filter_t<true, 1, true>(q, nblocks, lds_bytes, s, e0, e1);
-}
+template hipError_t launch_filter_t<true, 1, true>(const DevFilter &, int, size_t, hipStream_t, hipEvent_t, hipEvent_t);
 }  // namespace phip

@@ -1279,10 +1279,8 @@ __device__ __forceinline__ void fused_defer(cquery_t &aq, cseg_t &seg, const Til
 // (DictionaryBasedGroupKeyGenerator.java:285-414 keys, DefaultGroupByExecutor.java:116-140 holders). The tile masks
 // never reach HBM and the second launch with its mask walk is gone.
 // NA == kFusedGroupBy: one HBM table (agent-scope atomics); NA == kFusedGroupByXcd: its XCD-private copies (GB_XCD);
-// NA == kFusedGroupByLds: the workgroup's table in LDS after the rings, written to its slab at the end (GB_LDS).
-constexpr int kFusedGroupBy = -1;
-constexpr int kFusedGroupByXcd = -2;
-constexpr int kFusedGroupByLds = -3;
+// NA == kFusedGroupByLds: the workgroup's table in LDS after the rings, written to its slab at the end (GB_LDS)
+// (device.h holds the three values: filter.hip names the instantiations by them).
 constexpr int kGbFlush = 64 * kFusedBatchGB;
 static_assert(kFusedRingGB >= 2 * kGbFlush, "a piece of <= kGbFlush docs lands on < kGbFlush pending");
 

@@ -9,6 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "dev_common.h"
+#include "launch.h"
 
 namespace phip {
 

@@ -3,6 +3,7 @@
 
 #include "codec.h"
 #include "dev_common.h"
+#include "launch.h"
 
 namespace phip {
 

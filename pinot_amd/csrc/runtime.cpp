@@ -28,136 +28,8 @@
 
 #include "../../include/pinot_hip.h"
 #include "device.h"
+#include "launch.h"
 #include "node.h"
-
-namespace phip {
-hipError_t launch_bswap32(uint32_t *p, int64_t n, hipStream_t s);
-hipError_t launch_bswap64(uint64_t *p, int64_t n, hipStream_t s);
-hipError_t launch_trim_order(const double *vals, const int64_t *keys, const KeyOrder *ko, int64_t n, int32_t naggs,
-                             int32_t agg, int32_t desc, void *scratch, size_t *scratch_bytes, const int32_t **order_out,
-                             hipStream_t s);
-hipError_t launch_trim_order_terms(const double *vals, const int64_t *keys, const OrderTerms *ot, int64_t n,
-                                   int32_t naggs, const uint8_t *hll, int64_t hll_bytes, int32_t m_regs, void *scratch,
-                                   size_t *scratch_bytes, const int32_t **order_out, hipStream_t s);
-hipError_t launch_trim_gather(const int32_t *order, int64_t k, int32_t naggs, int64_t hll_bytes, const int64_t *keys,
-                              const double *vals, const int64_t *longs, const uint8_t *hll, int64_t *keys_out,
-                              double *vals_out, int64_t *longs_out, uint8_t *hll_out, hipStream_t s);
-hipError_t launch_chunk_decode(int codec, int entry, const uint8_t *blob, const RawChunk *chunks, int32_t nchunks,
-                               int32_t out_cap, int32_t in_cap, size_t lds, uint8_t *out, int32_t *err, int32_t *sizes,
-                               hipStream_t s);
-size_t chunk_decode_extra_lds(int codec, int32_t out_cap);
-hipError_t launch_sorted_to_packed(const uint32_t *be_pairs, int32_t card, int32_t *ids_tmp, int64_t n, int32_t bits,
-                                   uint32_t *words, int64_t nwords, hipStream_t s);
-hipError_t launch_fill_u64(uint64_t *p, int64_t n, uint64_t v, hipStream_t s);
-hipError_t launch_xcd_init(uint64_t *tab, int64_t words, int64_t G, const int32_t *kinds, hipStream_t s);
-hipError_t launch_xcd_merge(uint64_t *tab, int64_t words, int64_t G, const int32_t *kinds, uint32_t *hll,
-                            int64_t hll_words, hipStream_t s);
-hipError_t launch_roaring_or(const RoaringTask *tasks, const RoaringGroup *groups, int32_t ngroups, hipStream_t s);
-hipError_t launch_filter(const DevFilter &q, bool conj_only, int fused_naggs, int nblocks, size_t lds_bytes,
-                         hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-// the lean fused shape (filter.hip). Weak: the host simulation's stub library has launch_filter alone, and a plan then
-// keeps the general instantiation.
-__attribute__((weak)) hipError_t launch_filter_lean(const DevFilter &q, int fused_naggs, int nblocks, size_t lds_bytes,
-                                                    hipStream_t s, hipEvent_t e0, hipEvent_t e1);
-hipError_t launch_masks_to_words(const uint32_t *masks, int32_t tile0, int32_t ntiles, uint64_t *words, int64_t nwords,
-                                 hipStream_t s);
-hipError_t launch_agg(const DevAggQuery &q, const DevAggQuery *dq, int nblocks, size_t lds, hipStream_t s,
-                      hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-hipError_t launch_hash_keys(int64_t *slots, int64_t n, const uint64_t *keys, hipStream_t s);
-hipError_t launch_slab_reduce(const uint64_t *slab, int32_t nslabs, int32_t tbl_words, int64_t G, const int32_t *kinds,
-                              uint64_t *out, const uint32_t *hslab, int32_t hll_words, uint32_t *hout, hipStream_t s);
-hipError_t launch_finalize_partials2(const uint64_t *pa, int nba, int na, const int32_t *ka, uint64_t *oa,
-                                     const uint64_t *pb, int nbb, int nb, const int32_t *kb, uint64_t *ob, hipStream_t s);
-hipError_t launch_finalize_partials(const uint64_t *partials, int nblocks, int nslots, const int32_t *kinds,
-                                    uint64_t *out, hipStream_t s);
-hipError_t launch_finalize_all(const uint64_t *pa, int nba, int na, const int32_t *ka, const uint64_t *pf, int nbf,
-                               const int32_t *kf, uint64_t *segm, int nseg, uint32_t *hll, int hll_words, uint64_t *out,
-                               hipStream_t s, uint32_t *ticket = nullptr, uint64_t seq = 0);
-hipError_t launch_group_count(const uint64_t *counts, int64_t n, int32_t *chunk_counts, int64_t nchunks,
-                              int64_t *offsets, hipStream_t s);
-hipError_t launch_group_compact(const uint64_t *counts, int64_t n, const int64_t *offsets, int64_t nchunks,
-                                int64_t *keys, hipStream_t s);
-hipError_t launch_group_gather(const int64_t *keys, int64_t ngroups, int64_t ndense, int32_t naggs, int32_t own_count,
-                               const int32_t *kinds, const uint64_t *table, const uint32_t *hll, int32_t nhll,
-                               int32_t log2m, double *vals, int64_t *longs, uint8_t *hll_out, hipStream_t s);
-hipError_t launch_group_gather_mapped(const int64_t *keys, const int64_t *d_ngroups, int64_t ndense, int32_t naggs,
-                                      int32_t own_count, const int32_t *kinds, const uint64_t *table,
-                                      int64_t *out_count, int64_t *out_keys, double *vals, int64_t *longs,
-                                      const uint32_t *hll, int32_t nhll, int32_t log2m, uint32_t *hll_out,
-                                      hipStream_t s);
-hipError_t launch_select_count(const DevSelQuery *q, int64_t total_work, int64_t *tile_cnt, hipStream_t s);
-hipError_t launch_select_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, int64_t n, hipStream_t s);
-hipError_t launch_select_bases(const DevSelQuery *q, int64_t *seg_base, int64_t *kept, int64_t *total, hipStream_t s);
-hipError_t launch_select_str_lens(const uint64_t *loc, int64_t rows, const uint64_t *const *offs, uint32_t *lens,
-                                  hipStream_t s);
-hipError_t launch_select_str_bytes(const uint64_t *loc, int64_t rows, const uint8_t *const *strs,
-                                   const uint64_t *const *offs, const uint64_t *dst_off, uint8_t *dst, hipStream_t s);
-hipError_t launch_select_gather(const DevSelQuery *q, int64_t total_work, uint64_t *out, int64_t num_rows,
-                                hipStream_t s);
-// ... on at most max_blocks workgroups (PHIP_GRID_CUS). Weak: the host simulation's stub library has only the two
-// above, and a capped plan then takes them.
-__attribute__((weak)) hipError_t launch_select_count_capped(const DevSelQuery *q, int64_t total_work, int max_blocks,
-                                                            int64_t *tile_cnt, hipStream_t s);
-__attribute__((weak)) hipError_t launch_select_gather_capped(const DevSelQuery *q, int64_t total_work, int max_blocks,
-                                                             uint64_t *out, int64_t num_rows, hipStream_t s);
-// distinct.hip (exact DISTINCTCOUNT). Weak: a build of the host code without that file (the host simulation's stub
-// library) links, and a plan that holds a PHIP_AGG_DISTINCT is refused at creation ("distinct pass not built").
-__attribute__((weak)) hipError_t launch_distinct_mark(const DevDistinctQuery *q, int64_t total_work, int lds,
-                                                      size_t lds_bytes, int max_blocks, hipStream_t s);
-__attribute__((weak)) hipError_t launch_distinct_finish(const DevDistinctQuery *q, const int64_t *keys, int64_t num_out,
-                                                        int64_t *counts, uint32_t *out, hipStream_t s);
-hipError_t launch_limit_prepare(const int64_t *slots, int64_t n, const uint64_t *hkeys, const uint32_t *first_doc,
-                                int32_t nseg, uint64_t *sortkey, int32_t *idx, hipStream_t s);
-hipError_t launch_limit_bounds(const uint64_t *sk_sorted, int64_t n, int64_t *first, int64_t *last, hipStream_t s);
-hipError_t launch_sort_pairs(void *temp, size_t *temp_bytes, const uint64_t *k_in, uint64_t *k_out, const void *v_in,
-                             void *v_out, bool wide, int64_t n, int end_bit, hipStream_t s);
-hipError_t launch_limit_select(const uint64_t *sk_sorted, const int32_t *idx_sorted, int64_t n, const int64_t *seg_start,
-                               int64_t limit, const int64_t *slots, const uint64_t *hkeys, int32_t nseg, uint64_t *key2,
-                               int64_t *slot2, hipStream_t s);
-hipError_t launch_limit_runs(void *temp, size_t *scan_bytes, const uint64_t *k, int64_t n, int32_t *head, int32_t *run,
-                             hipStream_t s);
-hipError_t launch_limit_reduce(const uint64_t *k, const int64_t *slot2, int64_t n, const int32_t *head, const int32_t *run,
-                               int64_t cap, int32_t naggs, int32_t own_count, const int32_t *kinds,
-                               const uint64_t *table, const uint32_t *hll, int32_t nhll, int32_t log2m,
-                               int64_t *keys_out, double *vals, int64_t *longs, uint8_t *hll_out, hipStream_t s);
-hipError_t launch_raw_images(const void *raw, int32_t type, int64_t n, uint64_t *out, hipStream_t s);
-hipError_t launch_sort_unique_u64(void *temp, size_t *temp_bytes, uint64_t *in, uint64_t *sorted, uint64_t *out,
-                                  int64_t *num_out, int64_t n, hipStream_t s);
-hipError_t launch_str_hash_unique(void *temp, size_t *temp_bytes, const uint8_t *bytes, const uint64_t *off, int64_t n,
-                                  uint64_t *hash, int32_t *docs, uint64_t *hash_sorted, int32_t *docs_sorted,
-                                  uint64_t *uniq, int32_t *rep, int64_t *num_out, hipStream_t s);
-hipError_t launch_str_verify(const uint8_t *bytes, const uint64_t *off, int64_t n, const uint64_t *uniq, const int32_t *rep,
-                             int64_t u, int32_t *collided, hipStream_t s);
-hipError_t launch_str_rep_lens(const uint64_t *off, const int32_t *rep, int64_t u, uint32_t *lens, hipStream_t s);
-hipError_t launch_str_rep_bytes(const uint8_t *bytes, const uint64_t *off, const int32_t *rep, int64_t u,
-                                const uint64_t *dst_off, uint8_t *dst, hipStream_t s);
-hipError_t set_str_hash_bits(int bits);
-hipError_t launch_raw_str_ids(const uint8_t *bytes, const uint64_t *off, int64_t n, const uint64_t *uniq, int64_t u,
-                              const int32_t *map, int32_t *ids, hipStream_t s);
-hipError_t launch_tuple_words(const TupleCols &tc, int64_t n, uint64_t *out, hipStream_t s);
-hipError_t launch_tuple_rank(void *temp, size_t *temp_bytes, const uint64_t *words, int32_t nw, int64_t n, int32_t *ids,
-                             uint64_t *uniq, int64_t ucap, int64_t *num_out, hipStream_t s);
-hipError_t launch_gather_ids(const int32_t *local, const int32_t *map, int64_t n, int32_t *out, hipStream_t s);
-hipError_t launch_raw_key_ids(const void *raw, int32_t type, int64_t n, const uint64_t *uniq, int64_t u, int32_t *ids,
-                              hipStream_t s);
-hipError_t launch_materialize_hll16(const uint32_t *words, int32_t bits, const uint32_t *table, int64_t n, uint16_t *out,
-                                    hipStream_t s);
-hipError_t launch_materialize_record(const RecSrcs &fs, int nf, int64_t n, int W, uint32_t *out, hipStream_t s);
-hipError_t launch_minmax_i64(const void *raw, int32_t type, int64_t n, int64_t *out, hipStream_t s,
-                             const uint64_t *nulls = nullptr);
-hipError_t launch_chunk_decode_global(int codec, const uint8_t *blob, const RawChunk *chunks, int32_t nchunks, uint8_t *out,
-                                      int32_t *err, int32_t *sizes, uint8_t *lits, uint64_t lits_stride, hipStream_t s);
-hipError_t launch_bitslice(const uint32_t *words, int32_t bits, int64_t ntiles, uint32_t *planes, hipStream_t s);
-hipError_t launch_materialize_packed(const uint32_t *words, int32_t bits, const void *dict, int32_t width, int64_t n,
-                                     int64_t base, int32_t vbits, int64_t nwords, uint32_t *out, hipStream_t s);
-hipError_t launch_materialize(const uint32_t *words, int32_t bits, const void *dict, int32_t width, int64_t n,
-                              void *vals, hipStream_t s);
-hipError_t launch_varbyte_offsets(const uint8_t *stage, const uint64_t *chunk_base, const int32_t *chunk_size,
-                                  int32_t per_chunk, int64_t n, uint64_t *len, uint64_t *off, void *temp,
-                                  size_t *temp_bytes, int32_t *err, hipStream_t s);
-hipError_t launch_varbyte_copy(const uint8_t *stage, const uint64_t *chunk_base, const int32_t *chunk_size,
-                               int32_t per_chunk, int64_t n, const uint64_t *off, uint8_t *out, hipStream_t s);
-}  // namespace phip
 
 using namespace phip;
 
@@ -1196,8 +1068,6 @@ int validate_tree(const phip_filter_node *nodes, int begin, int end, int idx, in
   return after;
 }
 
-std::string dict_key(const ColumnStore &c) { return std::string((const char *)c.host_dict.data(), c.host_dict.size()); }
-
 // Total order of dictionary values as the reference sorts them: numbers by value (FLOAT / DOUBLE in
 // Float.compare / Double.compare order: -0.0 < 0.0, NaN last), strings as '\0'-padded bytes (memcmp order ==
 // String.compareTo for ASCII / BMP UTF-8).
@@ -2059,12 +1929,12 @@ struct Plan {
     uint32_t progs = 1;                      // bit p: filter program p projects the column
   };
   std::vector<ProjCol> proj;
-  bool has_filter = false, need_agg = false, need_mask = false, group_by = false, conj_only = false;
-  int fused_naggs = 0;  // > 0: the filter kernel aggregates (fused_tile), no aggregation launch
-  bool fused_lean = false;  // ... in its lean shape (filter_kernel.h kBsDefer): bit-sliced conjunctions, deferred gathers
-  bool fused_gb = false;  // the filter kernel runs the dense group-by into the HBM table (no aggregation launch)
-  bool gb_xcd = false;    // ... into kXcdCopies XCD-private copies of it (GB_XCD), merged after the launch
-  bool gb_lds = false;    // ... into each workgroup's LDS table (GB_LDS), its slabs reduced after the launch
+  bool has_filter = false, need_agg = false, need_mask = false, group_by = false;
+  FilterVariant variant = FV_GENERAL;  // the filter kernel's instantiation (launch.h), decided by prepare_plan
+  int fused_naggs = 0;                 // FV_FUSED / FV_FUSED_LEAN: the aggregations the filter kernel runs (fused_tile)
+  bool fused_agg() const { return variant == FV_FUSED || variant == FV_FUSED_LEAN; }
+  bool fused_gb() const { return variant == FV_GB || variant == FV_GB_XCD || variant == FV_GB_LDS; }
+  bool fused() const { return fused_agg() || fused_gb(); }  // one kernel filters and aggregates: no aggregation launch
   bool node_part = false;  // a node plan's part (node_plan_create): a hash table may go out as a partial table
   // GB_LDS walks: [0] the one-chunk walk, [1] the batched one (agg_kernel kDense) -- LDS bytes, workgroups and waves
   // per workgroup of each; walk_cur's is the launch's (agg_lds / agg_blocks / dq.dense_batch / dq.wg_waves), re-chosen
@@ -2473,8 +2343,6 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     d.program = ag.program;
     if (ag.function < PHIP_AGG_COUNT || ag.function > PHIP_AGG_DISTINCT) return fail(PHIP_ERR_INVALID, "bad aggregation function");
     if (ag.function == PHIP_AGG_DISTINCT) {  // the refusals of include/pinot_hip.h PHIP_AGG_DISTINCT
-      if (launch_distinct_mark == nullptr || launch_distinct_finish == nullptr)
-        return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT: distinct pass not built");
       if (ag.expr != PHIP_EXPR_COLUMN) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT of an expression");
       if (nprog > 1) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT beside several filter programs");
       if (q->null_group_by) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT beside null group keys");
@@ -3855,7 +3723,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // general instantiation 16 VGPR / 149 SGPR spills on the headline. Then no segment stages more than
   // its conjunction's planes (<= kMaxConj regions, the lean cursor's size). PHIP_FUSED_LEAN=0 keeps the general
   // instantiation (A/B).
-  bool fused_lean = fused_naggs > 0 && !fused_gb && conj_only && launch_filter_lean != nullptr;
+  bool fused_lean = fused_naggs > 0 && !fused_gb && conj_only;
   for (const DevSeg &ds : dsegs)
     fused_lean = fused_lean && (ds.conj == 0 || ds.conj_bs != 0) && ds.fused_defer == 1 && ds.num_stage <= kMaxConj;
   if (const char *le = getenv("PHIP_FUSED_LEAN")) fused_lean = fused_lean && atoi(le) != 0;
@@ -4317,12 +4185,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   P.need_mask = need_mask;
   P.group_by = group_by;
   P.node_part = tl_node_docs > 0;
-  P.conj_only = conj_only;
+  // (both fused shapes were decided for conjunctive programs only: conj_all, above)
+  P.variant = fused_gb          ? (gb_lds ? FV_GB_LDS : gb_xcd ? FV_GB_XCD : FV_GB)
+              : fused_naggs > 0 ? (fused_lean ? FV_FUSED_LEAN : FV_FUSED)
+                                : (conj_only ? FV_CONJ : FV_GENERAL);
   P.fused_naggs = fused_naggs;
-  P.fused_lean = fused_lean;
-  P.fused_gb = fused_gb;
-  P.gb_xcd = gb_xcd;
-  P.gb_lds = gb_lds;
   P.want_bitmap = want_bitmap;
   P.filter_nwords = filter_nwords;
   P.filter_blocks = filter_blocks;
@@ -4361,7 +4228,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   P.first_doc = (uint32_t *)first_doc;
   if (const char *te = getenv("PHIP_TOTAL_EVENTS")) P.total_events = atoi(te) != 0;
   // ev[4] only between two launches (selection plans time their gather with it, execute_select)
-  P.split_event = P.select || (P.has_filter && P.need_agg && P.fused_naggs == 0 && !P.fused_gb);
+  P.split_event = P.select || (P.has_filter && P.need_agg && !P.fused());
   if (const char *se = getenv("PHIP_SPLIT_EVENT")) P.split_event = P.split_event || atoi(se) != 0;  // A/B
   for (auto &e : P.ev) HIP_TRY(hipEventCreate(&e));
   {
@@ -4448,7 +4315,6 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   DevFilter &fq = P.fq;
   const int naggs = P.naggs, nhll = P.nhll, m_regs = P.m_regs;
   const bool group_by = P.group_by, has_filter = P.has_filter, need_agg = P.need_agg, need_mask = P.need_mask;
-  const bool conj_only = P.conj_only;
   const int64_t total_work = P.total_work;
   uint8_t *base = P.base;
   const int32_t *dev_kinds = (const int32_t *)(base + P.kinds_off);
@@ -4482,7 +4348,7 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
     HIP_TRY(hipMemsetAsync(dq.hash_overflow, 0, 4, st));
     if (P.first_doc) HIP_TRY(hipMemsetAsync(P.first_doc, 0xff, (size_t)dq.num_groups * 4, st));
   }
-  if (group_by && P.gb_xcd) {  // every XCD-private copy at its identity
+  if (group_by && P.variant == FV_GB_XCD) {  // every XCD-private copy at its identity
     HIP_TRY(launch_xcd_init((uint64_t *)gtab, dq.xcd_words, dq.num_groups, dev_kinds, st));
     if (nhll) HIP_TRY(hipMemsetAsync(ghll, 0, (size_t)kXcdCopies * dq.xcd_hll_words * 4, st));
   } else if (group_by && (dq.mode == GB_GLOBAL || dq.mode == GB_HASH)) {
@@ -4494,7 +4360,7 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
     }
     if (nhll) HIP_TRY(hipMemsetAsync(ghll, 0, (size_t)nhll * dq.num_groups * m_regs * 4, st));
   }
-  const bool fused = P.fused_naggs > 0 || P.fused_gb;
+  const bool fused = P.fused();
   // Opt-in (PHIP_EXT_EVENTS=1): a one-kernel plan's timing events recorded by the kernel's own dispatch packet
   // (hipExtLaunchKernel) instead of two barrier-packet markers. Measured on the sorted headline it costs more than it
   // saves: enqueue 7.0 -> 9.8 us per query, step 0.286 -> 0.304 ms (profiles/r04p_host_ab.log).
@@ -4505,11 +4371,8 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   const bool ext_events = P.timed && total_work > 0 && nkern == 1 && !P.split_event && xe && atoi(xe) != 0;
   hipEvent_t e0 = ext_events ? P.ev[1] : nullptr, e1 = ext_events ? P.ev[2] : nullptr;
   if (!ext_events && P.timed) HIP_TRY(hipEventRecord(P.ev[1], st));
-  if (has_filter && total_work > 0 && P.fused_lean)
-    HIP_TRY(launch_filter_lean(fq, P.fused_naggs, filter_blocks, filter_lds, st, e0, e1));
-  else if (has_filter && total_work > 0)
-    HIP_TRY(launch_filter(fq, conj_only, P.fused_gb ? (P.gb_lds ? -3 : (P.gb_xcd ? -2 : -1)) : P.fused_naggs, filter_blocks,
-                          filter_lds, st, e0, e1));
+  if (has_filter && total_work > 0)
+    HIP_TRY(launch_filter(fq, P.variant, P.fused_naggs, filter_blocks, filter_lds, st, e0, e1));
   // (a plan of one kernel -- fused, or a filter or aggregation alone -- needs no split event)
   if (P.split_event && P.timed) HIP_TRY(hipEventRecord(P.ev[4], st));
   if (need_agg && total_work > 0 && !fused)
@@ -4524,13 +4387,13 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
                                  P.dist_blocks, st));
     if (P.timed) HIP_TRY(hipEventRecord(P.dist_ev[1], st));
   }
-  if (group_by && P.gb_xcd && total_work > 0)  // the XCD-private copies folded into copy 0 (the plan's table)
+  if (group_by && P.variant == FV_GB_XCD && total_work > 0)  // the XCD-private copies folded into copy 0 (the plan's table)
     HIP_TRY(launch_xcd_merge((uint64_t *)gtab, dq.xcd_words, dq.num_groups, dev_kinds, (uint32_t *)ghll,
                              dq.xcd_hll_words, st));
   if (group_by && dq.mode == GB_LDS && total_work > 0)
-    HIP_TRY(launch_slab_reduce((const uint64_t *)slab, P.gb_lds ? filter_blocks : agg_blocks, dq.tbl_words, dq.num_groups,
-                               dev_kinds,
-                               (uint64_t *)gtab, (const uint32_t *)hslab, nhll ? dq.hll_words : 0, (uint32_t *)ghll, st));
+    HIP_TRY(launch_slab_reduce((const uint64_t *)slab, P.variant == FV_GB_LDS ? filter_blocks : agg_blocks, dq.tbl_words,
+                               dq.num_groups, dev_kinds, (uint64_t *)gtab, (const uint32_t *)hslab,
+                               nhll ? dq.hll_words : 0, (uint32_t *)ghll, st));
   if (group_by && dq.mode == GB_LDS && total_work == 0) {
     // nothing to reduce: the table holds every row's identity (a partial table is merged row by row)
     HIP_TRY(hipMemsetAsync(gtab, 0, (size_t)dq.num_groups * 8, st));
@@ -4630,7 +4493,7 @@ static int32_t group_limit(Plan &P, Workspace &ws, hipStream_t st, int64_t match
   for (int a = 0; a < naggs; a++)
     HIP_TRY(launch_fill_u64((uint64_t *)tab + (int64_t)(1 + a) * cap, cap, dq.aggs[a].acc == ACC_MIN_F64 ? ~0ull : 0ull, st));
   if (nhll) HIP_TRY(hipMemsetAsync(hll, 0, (size_t)nhll * cap * m_regs * 4, st));
-  if (P.fused_gb && P.total_work > 0) {
+  if (P.fused_gb() && P.total_work > 0) {
     // the fused group-by left no tile masks: the plain conjunctive filter writes them into scratch (its matched-doc
     // counts and partials into scratch too: the statistics were read after the normal pass)
     void *lm, *lp, *ls;
@@ -4644,7 +4507,7 @@ static int32_t group_limit(Plan &P, Workspace &ws, hipStream_t st, int64_t match
     fq.mask_out = (uint32_t *)lm;
     fq.partials = (uint64_t *)lp;
     fq.seg_matched = (uint64_t *)ls;
-    HIP_TRY(launch_filter(fq, true, 0, P.filter_blocks, P.filter_lds, st, nullptr, nullptr));
+    HIP_TRY(launch_filter(fq, FV_CONJ, 0, P.filter_blocks, P.filter_lds, st));
     dq.mask = (const uint32_t *)lm;
   }
   HIP_TRY(hipMemcpyAsync(ddq, &dq, sizeof(dq), hipMemcpyHostToDevice, st));
@@ -4759,10 +4622,7 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     HIP_TRY(launch_select_scan(nullptr, &tb, nullptr, nullptr, tw + 1, st));
     void *tmp;
     if ((rc = ws.get("sel_scan", std::max<size_t>(tb, 16), &tmp))) return rc;
-    if (P.sel_max_blocks < 4096 && launch_select_count_capped)
-      HIP_TRY(launch_select_count_capped(dsq, tw, P.sel_max_blocks, P.sel_tile_cnt, st));
-    else
-      HIP_TRY(launch_select_count(dsq, tw, P.sel_tile_cnt, st));
+    HIP_TRY(launch_select_count(dsq, tw, P.sel_max_blocks, P.sel_tile_cnt, st));
     HIP_TRY(launch_select_scan(tmp, &tb, P.sel_tile_cnt, P.sel_tile_off, tw + 1, st));
     HIP_TRY(launch_select_bases(dsq, P.sel_base, P.sel_kept, P.sel_total, st));
     HIP_TRY(hipMemcpyAsync(tot, P.sel_total, 16, hipMemcpyDeviceToHost, st));
@@ -4775,10 +4635,7 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     void *out;
     if ((rc = ws.get("sel_out", (size_t)rows * P.nsel * 8, &out))) return rc;
     HIP_TRY(hipEventRecord(P.ev[4], st));
-    if (P.sel_max_blocks < 4096 && launch_select_gather_capped)
-      HIP_TRY(launch_select_gather_capped(dsq, tw, P.sel_max_blocks, (uint64_t *)out, rows, st));
-    else
-      HIP_TRY(launch_select_gather(dsq, tw, (uint64_t *)out, rows, st));
+    HIP_TRY(launch_select_gather(dsq, tw, P.sel_max_blocks, (uint64_t *)out, rows, st));
     HIP_TRY(hipEventRecord(P.ev[2], st));
     HIP_TRY(hipMemcpyAsync(impl.sel_values.data(), out, (size_t)rows * P.nsel * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4942,7 +4799,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (mode != EXEC_FINISH) {
     const int32_t sh[PHIP_LAUNCH_SHAPE_VALUES] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves,
                                                   P.fq.nbuf, (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks,
-                                                  P.fused_lean ? 1 : 0};
+                                                  P.variant == FV_FUSED_LEAN ? 1 : 0};
     memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {
@@ -5378,7 +5235,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   } else if (P.split_event) {
     HIP_TRY(hipEventElapsedTime(&t_filter, P.ev[1], P.ev[4]));
     HIP_TRY(hipEventElapsedTime(&t_agg, P.ev[4], P.ev[2]));
-  } else if (has_filter && !(need_agg && !P.fused_naggs && !P.fused_gb)) {
+  } else if (has_filter && !(need_agg && !P.fused())) {
     t_filter = t_scan;  // the one kernel between ev[1] and ev[2] is the filter (fused or not)
   } else {
     t_agg = t_scan;
@@ -5401,7 +5258,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     }
     r.agg_bytes = ab;
   }
-  if (P.fused_naggs > 0 || P.fused_gb) {  // one kernel filtered and aggregated: it owns both times and both byte counts
+  if (P.fused()) {  // one kernel filtered and aggregated: it owns both times and both byte counts
     r.fused = 1;
     r.filter_kernel_ms = t_filter + t_agg;
     r.agg_kernel_ms = 0.0;

@@ -16,6 +16,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "agg_common.h"
+#include "launch.h"
 
 namespace phip {
 
@@ -126,17 +127,13 @@ __global__ __launch_bounds__(kSelBlock) void select_gather_kernel(const DevSelQu
 }
 
 // ---- host-callable launchers (runtime.cpp execute_select) ------------------------------------------------------
-static inline int sel_blocks(int64_t total_work, int max_blocks = 4096) {
+static inline int sel_blocks(int64_t total_work, int max_blocks) {
   const int64_t b = (total_work + kSelWaves - 1) / kSelWaves;
   return (int)(b < 1 ? 1 : (b > max_blocks ? max_blocks : b));
 }
 
-hipError_t launch_select_count(const DevSelQuery *q, int64_t total_work, int64_t *tile_cnt, hipStream_t s) {
-  select_count_kernel<<<sel_blocks(total_work), kSelBlock, 0, s>>>(q, tile_cnt);
-  return hipGetLastError();
-}
-hipError_t launch_select_count_capped(const DevSelQuery *q, int64_t total_work, int max_blocks, int64_t *tile_cnt,
-                                      hipStream_t s) {
+hipError_t launch_select_count(const DevSelQuery *q, int64_t total_work, int max_blocks, int64_t *tile_cnt,
+                               hipStream_t s) {
   select_count_kernel<<<sel_blocks(total_work, max_blocks), kSelBlock, 0, s>>>(q, tile_cnt);
   return hipGetLastError();
 }
@@ -185,14 +182,8 @@ hipError_t launch_select_str_bytes(const uint64_t *loc, int64_t rows, const uint
   return hipGetLastError();
 }
 
-hipError_t launch_select_gather(const DevSelQuery *q, int64_t total_work, uint64_t *out, int64_t num_rows,
-                                hipStream_t s) {
-  if (num_rows <= 0 || total_work <= 0) return hipSuccess;
-  select_gather_kernel<<<sel_blocks(total_work), kSelBlock, 0, s>>>(q, out, num_rows);
-  return hipGetLastError();
-}
-hipError_t launch_select_gather_capped(const DevSelQuery *q, int64_t total_work, int max_blocks, uint64_t *out,
-                                       int64_t num_rows, hipStream_t s) {
+hipError_t launch_select_gather(const DevSelQuery *q, int64_t total_work, int max_blocks, uint64_t *out,
+                                int64_t num_rows, hipStream_t s) {
   if (num_rows <= 0 || total_work <= 0) return hipSuccess;
   select_gather_kernel<<<sel_blocks(total_work, max_blocks), kSelBlock, 0, s>>>(q, out, num_rows);
   return hipGetLastError();

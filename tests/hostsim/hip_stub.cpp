@@ -45,6 +45,7 @@ const char *hipGetErrorString(hipError_t) { return "stub"; }
 }
 
 #include "../../pinot_amd/csrc/device.h"
+#include "../../pinot_amd/csrc/launch.h"
 #include "../../pinot_amd/csrc/node.h"
 namespace phip {
 // node_merge.hip on the host (device memory is host memory here): the merges really run, so a node plan's merged
@@ -192,10 +193,10 @@ hipError_t launch_raw_key_ids(const void *, int32_t, int64_t, const uint64_t *, 
 }
 hipError_t launch_xcd_merge(uint64_t *, int64_t, int64_t, const int32_t *, uint32_t *, int64_t, hipStream_t) { return hipSuccess; }
 hipError_t launch_roaring_or(const RoaringTask *, const RoaringGroup *, int32_t, hipStream_t) { return hipSuccess; }
-hipError_t launch_filter(const DevFilter &q, bool, int fused_naggs, int nblocks, size_t, hipStream_t, hipEvent_t,
-                         hipEvent_t) {
+hipError_t launch_filter(const DevFilter &q, FilterVariant variant, int naggs, int nblocks, size_t, hipStream_t,
+                         hipEvent_t, hipEvent_t) {
   memset(q.partials, 0, (size_t)nblocks * 2 * 8);
-  if (fused_naggs > 0) memset(q.agg_partials, 0, (size_t)nblocks * fused_naggs * 8);
+  if (variant == FV_FUSED || variant == FV_FUSED_LEAN) memset(q.agg_partials, 0, (size_t)nblocks * naggs * 8);
   if (q.mask_out) memset(q.mask_out, 0, (size_t)q.total_work * 64 * 4);
   return hipSuccess;
 }
@@ -218,12 +219,6 @@ hipError_t launch_slab_reduce(const uint64_t *slab, int32_t, int32_t tbl_words, 
   if (hll_words) memset(hout, 0, (size_t)hll_words * 16);
   return hipSuccess;
 }
-hipError_t launch_finalize_partials2(const uint64_t *, int, int na, const int32_t *, uint64_t *oa, const uint64_t *, int,
-                                     int nb, const int32_t *, uint64_t *ob, hipStream_t) {
-  for (int i = 0; i < na; i++) oa[i] = 0;
-  for (int i = 0; i < nb; i++) ob[i] = 0;
-  return hipSuccess;
-}
 hipError_t launch_finalize_all(const uint64_t *, int, int na, const int32_t *, const uint64_t *, int, const int32_t *,
                                uint64_t *segm, int nseg, uint32_t *hll, int hll_words, uint64_t *out, hipStream_t,
                                uint32_t *ticket, uint64_t seq) {
@@ -237,9 +232,6 @@ hipError_t launch_finalize_all(const uint64_t *, int, int na, const int32_t *, c
   }
   (void)na;
   return hipSuccess;
-}
-hipError_t launch_finalize_partials(const uint64_t *, int, int nslots, const int32_t *, uint64_t *out, hipStream_t) {
-  memset(out, 0, nslots * 8); return hipSuccess;
 }
 hipError_t launch_group_count(const uint64_t *counts, int64_t n, int32_t *cc, int64_t nchunks, int64_t *offs, hipStream_t) {
   int64_t s = 0;
@@ -286,7 +278,7 @@ hipError_t launch_limit_runs(void *, size_t *scan_bytes, const uint64_t *, int64
 hipError_t launch_limit_reduce(const uint64_t *, const int64_t *, int64_t, const int32_t *, const int32_t *, int64_t,
                                int32_t, int32_t, const int32_t *, const uint64_t *, const uint32_t *, int32_t, int32_t, int64_t *,
                                double *, int64_t *, uint8_t *, hipStream_t) { return hipSuccess; }
-hipError_t launch_select_count(const DevSelQuery *, int64_t, int64_t *, hipStream_t) { return hipSuccess; }
+hipError_t launch_select_count(const DevSelQuery *, int64_t, int, int64_t *, hipStream_t) { return hipSuccess; }
 hipError_t launch_select_scan(void *, size_t *temp_bytes, const int64_t *, int64_t *, int64_t, hipStream_t) {
   *temp_bytes = 256; return hipSuccess;
 }
@@ -294,7 +286,15 @@ hipError_t launch_select_bases(const DevSelQuery *q, int64_t *, int64_t *kept, i
   for (int e = 0; e < q->num_segs; e++) kept[e] = 0;
   total[0] = total[1] = 0; return hipSuccess;
 }
-hipError_t launch_select_gather(const DevSelQuery *, int64_t, uint64_t *, int64_t, hipStream_t) { return hipSuccess; }
+hipError_t launch_select_gather(const DevSelQuery *, int64_t, int, uint64_t *, int64_t, hipStream_t) { return hipSuccess; }
+// (mark zeroes nothing: the host's memset clears the bitmap before it)
+hipError_t launch_distinct_mark(const DevDistinctQuery *, int64_t, int, size_t, int, hipStream_t) { return hipSuccess; }
+hipError_t launch_distinct_finish(const DevDistinctQuery *q, const int64_t *, int64_t num_out, int64_t *counts, uint32_t *out,
+                                  hipStream_t) {
+  memset(counts, 0, (size_t)num_out * q->num_slots * 8);
+  memset(out, 0, (size_t)num_out * (size_t)q->row_words * 4);
+  return hipSuccess;
+}
 hipError_t launch_select_str_lens(const uint64_t *, int64_t, const uint64_t *const *, uint32_t *, hipStream_t) { return hipSuccess; }
 hipError_t launch_select_str_bytes(const uint64_t *, int64_t, const uint8_t *const *, const uint64_t *const *, const uint64_t *, uint8_t *,
                                    hipStream_t) { return hipSuccess; }
