@@ -189,6 +189,27 @@ typedef struct phip_filter_node {
  * PHIP_DISTINCT_LDS_WORDS (environment, read at plan creation, default 8192): without a group-by, bitmaps of at most
  * this many words in all are combined per workgroup in LDS and flushed with one global atomic OR per non-zero word;
  * larger ones, and every group-by, set bits in the global bitmap directly (test before set). */
+#define PHIP_AGG_VALUE_COUNTS 6 /* per-id value counts: the exact multiset PERCENTILE and MODE are computed from */
+/* PHIP_AGG_VALUE_COUNTS (PercentileAggregationFunction.java:77-100 keeps every value in a DoubleArrayList and :155-172
+ * sorts and indexes it; ModeAggregationFunction.java:81-155 keeps a value -> count map): a distinct slot that holds a
+ * u32 COUNT per query-global dictionary id where a PHIP_AGG_DISTINCT slot holds a bit. Slots of both kinds are numbered
+ * together in aggregation order and share a group's row (phip_result.reserved_distinct tells them apart):
+ *   slot s of a row = row + distinct_word_offsets[s], card_s u32 words; word i = the number of matched docs of the
+ *                     group whose value is entry i of phip_result_distinct_dictionary(result, s).
+ * values[] / long_values[] hold the sum of the slot's words = the docs aggregated (long_exact = 1). The words over the
+ * returned dictionary are the mergeable intermediate: two results merge by adding the counts of equal VALUES. The
+ * caller computes PERCENTILE (walk the values in order by cumulative count) and MODE (the values of maximal count) from
+ * them; several percentiles and modes of one column need one aggregation. No value is gathered on the device.
+ * Everything PHIP_AGG_DISTINCT refuses is refused here too (PHIP_DISTINCT_MAX_BYTES counts such a slot at 4 bytes per
+ * id), and besides: a STRING column (PHIP_ERR_UNSUPPORTED), and segments of 2^32 docs or more in all (a u32 count could
+ * wrap). Regimes as for PHIP_AGG_DISTINCT: in LDS (no group-by, the row within PHIP_DISTINCT_LDS_WORDS) every workgroup
+ * adds into its own copy and flushes each non-zero word with one global atomic add; otherwise one global atomic add per
+ * doc, lanes of a wave that hold the same id and row combined into one add when the dictionary is small
+ * (PHIP_COUNTS_COMBINE_CARD, default 64 ids, 0 = never; PHIP_COUNTS_COMBINE_ROUNDS, default 16: environment, read at
+ * plan creation, measurement overrides).
+ * PERCENTILEEST / PERCENTILETDIGEST / PERCENTILEKLL, raw columns and expression arguments are not on this path. */
+#define PHIP_DISTINCT_SLOT_BITS 0   /* bit s of phip_result.reserved_distinct: a PHIP_AGG_DISTINCT slot, ceil(card / 32) words */
+#define PHIP_DISTINCT_SLOT_COUNTS 1 /* a PHIP_AGG_VALUE_COUNTS slot, card words */
 
 #define PHIP_EXPR_COLUMN 0 /* a */
 #define PHIP_EXPR_ADD 1    /* a + b   (AdditionTransformFunction) */
@@ -348,9 +369,11 @@ typedef struct phip_result {
    * all segments -- the reference's numDocsScanned when programs are the plan maker's own device (the null-handling
    * group-by's IS NOT NULL programs), not FilteredGroupByOperator infos. For a phip_plan_finish result: this GPU's. */
   const int64_t *program_docs_matched;
-  /* PHIP_AGG_DISTINCT (see its definition above): the number of distinct slots, the groups' bitmap rows back to back
-   * (num_groups x distinct_word_offsets[num_distinct] words) and the num_distinct + 1 word offsets of the slots
-   * inside a row. NULL / 0 without a DISTINCT aggregation. */
+  /* PHIP_AGG_DISTINCT / PHIP_AGG_VALUE_COUNTS (see their definitions above): the number of distinct slots, the
+   * groups' rows back to back (num_groups x distinct_word_offsets[num_distinct] words) and the num_distinct + 1 word
+   * offsets of the slots inside a row. NULL / 0 without such an aggregation. reserved_distinct holds the slots' kinds:
+   * bit s set = slot s is a PHIP_AGG_VALUE_COUNTS slot (PHIP_DISTINCT_SLOT_COUNTS: card_s words of u32 counts), clear =
+   * a PHIP_AGG_DISTINCT slot (PHIP_DISTINCT_SLOT_BITS: ceil(card_s / 32) bitmap words). At most 8 slots per plan. */
   int32_t num_distinct;
   int32_t reserved_distinct;
   const uint32_t *distinct_words;

@@ -31,7 +31,8 @@ class RawRange(ctypes.Structure):
                 ("hi_real", ctypes.c_double), ("lo_inclusive", ctypes.c_int32), ("hi_inclusive", ctypes.c_int32)]
 
 
-AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_HLL, AGG_DISTINCT = range(6)
+AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_HLL, AGG_DISTINCT, AGG_VALUE_COUNTS = range(7)
+DISTINCT_SLOT_BITS, DISTINCT_SLOT_COUNTS = range(2)  # bit s of phip_result.reserved_distinct: slot s's kind
 EXPR_COLUMN, EXPR_ADD, EXPR_SUB, EXPR_MUL = range(4)
 
 EXPORTED_SYMBOLS = (

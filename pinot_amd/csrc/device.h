@@ -74,7 +74,8 @@ enum AccKind : int32_t {
   ACC_MIN_F64 = 3,
   ACC_MAX_F64 = 4,
   ACC_HLL = 5,      // registers, per (group, hll slot)
-  ACC_DISTINCT = 6, // exact DISTINCTCOUNT: a dictionary-id bitmap per (group, distinct slot), filled by distinct.hip.
+  ACC_DISTINCT = 6, // exact DISTINCTCOUNT / value counts (PERCENTILE, MODE): a dictionary-id bitmap or a u32 count per
+                    // id, per (group, distinct slot), filled by distinct.hip.
                     // Host only: the descriptors the filter / aggregation kernels read carry such a slot as ACC_COUNT
                     // (a COUNT is row 0 / the matched docs: no kernel accumulates a row for it)
 };
@@ -403,9 +404,12 @@ struct DevSelQuery {
 };
 
 // Exact DISTINCTCOUNT (distinct.hip): a pass of its own over the filter's tile masks that sets, per matched doc and
-// distinct slot, bit `global id` of the doc's group row in one device bitmap [num_rows][row_words] u32.
+// distinct slot, bit `global id` of the doc's group row in one device bitmap [num_rows][row_words] u32. A slot of kind
+// counts (PHIP_AGG_VALUE_COUNTS: PERCENTILE, MODE) holds a u32 count per global id in the same row instead.
 constexpr int kMaxDistinct = kMaxAggs;
 constexpr int kDistinctLdsWords = 8192;  // default PHIP_DISTINCT_LDS_WORDS: 32 KiB of LDS per workgroup
+constexpr int kCountsCombineCard = 64;   // default PHIP_COUNTS_COMBINE_CARD (DevDistinctQuery.combine_card)
+constexpr int kCountsCombineRounds = 16; // default PHIP_COUNTS_COMBINE_ROUNDS (DevDistinctQuery.combine_rounds)
 struct DevDistinctQuery {
   const DevSeg *segs;
   int32_t num_segs;
@@ -413,14 +417,18 @@ struct DevDistinctQuery {
   const uint32_t *mask;  // [total_work][64] lane-major tile masks of the filter kernel; null = every doc
   uint32_t *bitmap;      // [num_rows][row_words]; bit i of word slot_off[s] + w of a row = global id 32 w + i of slot s
   int64_t num_rows;      // dense group-by key space (1 without a group-by)
-  int64_t row_words;     // sum over the slots of ceil(card_s / 32)
+  int64_t row_words;     // sum over the slots of ceil(card_s / 32) (bits) or card_s (counts)
   int32_t num_slots;
   int32_t lds;           // 1: no group-by and row_words fit the LDS budget -- each workgroup ORs into an LDS copy
   int32_t slot_col[kMaxDistinct];   // the slot's column (DevSeg.cols index)
   int32_t slot_card[kMaxDistinct];  // its query-global cardinality
+  int32_t slot_kind[kMaxDistinct];  // PHIP_DISTINCT_SLOT_BITS: bit `gid` of the slot's words; PHIP_DISTINCT_SLOT_COUNTS
+                                    // (PHIP_AGG_VALUE_COUNTS): word `gid` = the matched docs whose global id is gid
   int64_t slot_off[kMaxDistinct];   // its first word inside a row
   int32_t num_group_by;
-  int32_t pad;
+  int32_t combine_card;  // lds = 0: counts slots of at most this cardinality add once per equal (row, id) of a wave
+                         // (0: never) ...
+  int32_t combine_rounds;  // ... in at most this many rounds of peeling equal words; lanes left after them add 1 each
   int32_t gb_cols[kMaxGroupBy];
   int64_t gb_stride[kMaxGroupBy];   // the dense group-by's mixed radix (DevAggQuery.gb_stride)
 };

@@ -19,6 +19,14 @@
 //   2. distinct_finish_kernel  for the groups the result returns: popcount of every slot's words -> the count, and the
 //                              rows gathered back to back (phip_result.distinct_words).
 // Integer OR is order-free, so the bitmaps are bit-reproducible whatever the schedule.
+//
+// Value counts (PHIP_AGG_VALUE_COUNTS, the multiset behind PERCENTILE and MODE: PercentileAggregationFunction.java:
+// 77-100 collects every value, ModeAggregationFunction.java:81-155 a value -> count map) are the same pass with a u32
+// COUNT per (group, global id) where DISTINCTCOUNT keeps a bit: a counts slot is card_s words of the row, word gid = the
+// matched docs whose id is gid. lds = 1 adds 1 in LDS (no return value) and flushes each non-zero word with one global
+// atomic ADD; lds = 0 is one global atomic add per doc (test-before-set does not apply to a count). Bits and counts
+// slots share a row; the kind is per slot (DevDistinctQuery.slot_kind), so a branch on it is wave-uniform. Integer adds
+// are order-free too. The finish kernel returns the 64-bit sum of a counts slot's words (= the docs aggregated).
 #include "agg_common.h"
 #include "launch.h"
 
@@ -28,6 +36,11 @@ typedef const PHIP_CAS DevDistinctQuery cdst_t;
 
 constexpr int kDstBlock = 256;
 constexpr int kDstWaves = kDstBlock / kWave;
+
+// u32 words of slot s inside a row: a bit per global id, or a count per global id
+__device__ __forceinline__ int32_t slot_words(cdst_t &q, int s) {
+  return q.slot_kind[s] == PHIP_DISTINCT_SLOT_COUNTS ? q.slot_card[s] : (q.slot_card[s] + 31) >> 5;
+}
 
 // Dense group key of one doc, by the dense group-by's rule for dictionary keys (agg_common.h group_key): mixed radix
 // over query-global ids, column 0 least significant = the group's index in gb_table. Raw keys, doc-order key ids and
@@ -92,6 +105,33 @@ __global__ __launch_bounds__(kDstBlock) void distinct_mark_kernel(const DevDisti
         const uint32_t id = col_dict_id(c, doc);
         const uint32_t gid = c.remap ? (uint32_t)((const PHIP_GLB int32_t *)c.remap)[id] : id;
         if (gid >= (uint32_t)q.slot_card[s]) continue;  // (guard, as above)
+        if (q.slot_kind[s] == PHIP_DISTINCT_SLOT_COUNTS) {  // (wave-uniform: the slot's kind)
+          // word `gid` of the slot counts the docs. In LDS a plain add per lane (ds_add, no return value) is the fastest
+          // form measured, whatever the skew. A global row of a small dictionary puts many of the wave's lanes on one
+          // word, and same-address atomics serialise at the L2: there the lanes that share a word are peeled off
+          // together (the first active lane's word broadcast, its holders balloted) and ONE of them adds their number.
+          // At most combine_rounds rounds; lanes still left (many rows x ids in one wave) add 1 each.
+          const uint64_t w = (kLds ? 0ull : (uint64_t)key * (uint64_t)q.row_words) + (uint64_t)q.slot_off[s] + gid;
+          uint32_t add = 1u;
+          if (!kLds && q.slot_card[s] <= q.combine_card) {
+            bool pending = true;
+            for (int r = 0; r < q.combine_rounds && pending; r++) {
+              const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
+              const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32));
+              const bool mine = w == (((uint64_t)hi << 32) | lo);
+              const uint64_t same = ballot(mine);  // (of the lanes still pending: the holders of this word)
+              if (mine) {
+                add = mbcnt64(same) == 0 ? (uint32_t)__popcll(same) : 0u;
+                pending = false;
+              }
+            }
+          }
+          if (add) {
+            if (kLds) (void)__hip_atomic_fetch_add((lds_u32 *)&dst_lds[w], add, PHIP_RLX, PHIP_WG);
+            else (void)__hip_atomic_fetch_add((glb_u32 *)(q.bitmap + w), add, PHIP_RLX, PHIP_AG);
+          }
+          continue;
+        }
         const uint32_t bit = 1u << (gid & 31);
         if (kLds) {
           (void)__hip_atomic_fetch_or((lds_u32 *)&dst_lds[q.slot_off[s] + (gid >> 5)], bit, PHIP_RLX, PHIP_WG);
@@ -103,9 +143,15 @@ __global__ __launch_bounds__(kDstBlock) void distinct_mark_kernel(const DevDisti
   }
   if (kLds) {
     __syncthreads();
-    for (int32_t i = threadIdx.x; i < row_words; i += kDstBlock) {
-      const uint32_t v = dst_lds[i];
-      if (v) (void)__hip_atomic_fetch_or((glb_u32 *)(q.bitmap + i), v, PHIP_RLX, PHIP_AG);
+    for (int s = 0; s < q.num_slots; s++) {
+      const bool counts = q.slot_kind[s] == PHIP_DISTINCT_SLOT_COUNTS;
+      const int32_t off = (int32_t)q.slot_off[s], n = slot_words(q, s);
+      for (int32_t i = threadIdx.x; i < n; i += kDstBlock) {
+        const uint32_t v = dst_lds[off + i];
+        if (!v) continue;
+        if (counts) (void)__hip_atomic_fetch_add((glb_u32 *)(q.bitmap + off + i), v, PHIP_RLX, PHIP_AG);
+        else (void)__hip_atomic_fetch_or((glb_u32 *)(q.bitmap + off + i), v, PHIP_RLX, PHIP_AG);
+      }
     }
   }
 }
@@ -124,14 +170,15 @@ __global__ __launch_bounds__(kDstBlock) void distinct_finish_kernel(const DevDis
     const uint32_t *row = q.bitmap + (size_t)(ok ? key : 0) * (size_t)q.row_words;
     uint32_t *dst = out + (size_t)g * (size_t)q.row_words;
     for (int s = 0; s < q.num_slots; s++) {
-      const int64_t off = q.slot_off[s], n = ((int64_t)q.slot_card[s] + 31) >> 5;
-      uint32_t cnt = 0;
+      const int64_t off = q.slot_off[s], n = slot_words(q, s);
+      const bool counts_slot = q.slot_kind[s] == PHIP_DISTINCT_SLOT_COUNTS;
+      uint64_t cnt = 0;  // bits: the set bits; counts: the sum of the words = the docs aggregated
       for (int64_t i = lane; i < n; i += kWave) {
         const uint32_t v = ok ? row[off + i] : 0u;
         dst[off + i] = v;
-        cnt += (uint32_t)__popc(v);
+        cnt += counts_slot ? v : (uint32_t)__popc(v);
       }
-      cnt = wave_sum_u32(cnt);
+      for (int o = 32; o > 0; o >>= 1) cnt += (uint64_t)__shfl_xor((long long)cnt, o);
       if (lane == 0) counts[g * q.num_slots + s] = (int64_t)cnt;
     }
   }

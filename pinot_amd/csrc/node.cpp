@@ -688,10 +688,12 @@ int32_t node_create(const phip_query_desc *q, uint64_t *out_plan) {
   if (q->num_select > 0) return node_fail(PHIP_ERR_UNSUPPORTED, "selection over segments on several devices");
   if (q->num_aggregations < 0 || q->num_aggregations > 64 || q->num_group_by < 0 || q->num_group_by > 64)
     return node_fail(PHIP_ERR_INVALID, "query: bad aggregation / group-by counts");
-  // (a DISTINCTCOUNT's bitmaps are keyed by one device's query-global dictionary: no merge across parts yet)
+  // (a DISTINCTCOUNT's bitmaps and a PERCENTILE / MODE's value counts are keyed by one device's query-global
+  // dictionary: no merge across parts yet)
   for (int a = 0; a < q->num_aggregations && q->aggregations; a++)
-    if (q->aggregations[a].function == PHIP_AGG_DISTINCT)
-      return node_fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT in a node plan (several devices or PHIP_NODE_SPLIT)");
+    if (q->aggregations[a].function == PHIP_AGG_DISTINCT || q->aggregations[a].function == PHIP_AGG_VALUE_COUNTS)
+      return node_fail(PHIP_ERR_UNSUPPORTED,
+                       "DISTINCTCOUNT / value counts in a node plan (several devices or PHIP_NODE_SPLIT)");
   auto np = std::make_unique<NodePlan>();
   np->nseg = q->num_segments;
   np->nprog = std::max(1, q->num_filter_programs);

@@ -989,7 +989,7 @@ struct ResultImpl {
   std::vector<uint64_t> sel_values;  // selection: [num_select][num_rows]
   std::vector<int32_t> sel_types;
   std::vector<std::shared_ptr<Device::Remap>> sel_dicts;  // per select column: query-global dictionary (STRING)
-  std::vector<uint32_t> dist_words;    // DISTINCTCOUNT: [num_groups][dist_offsets.back()] bitmap words
+  std::vector<uint32_t> dist_words;    // DISTINCTCOUNT / value counts: [num_groups][dist_offsets.back()] words
   std::vector<int64_t> dist_offsets;   // [num_distinct + 1] word offsets of the slots inside a group's row
   std::vector<std::shared_ptr<Device::Remap>> dist_dicts;  // per distinct slot: its query-global dictionary
   std::vector<int64_t> seg_docs;  // per segment: matched docs summed over the filter programs
@@ -1858,10 +1858,15 @@ int acc_kind_for(const phip_aggregation &a, bool integral) {
     case PHIP_AGG_SUM: return integral ? ACC_SUM_I64 : ACC_SUM_F64;
     case PHIP_AGG_MIN: return ACC_MIN_F64;
     case PHIP_AGG_MAX: return ACC_MAX_F64;
-    case PHIP_AGG_DISTINCT: return ACC_DISTINCT;
+    case PHIP_AGG_DISTINCT:
+    case PHIP_AGG_VALUE_COUNTS: return ACC_DISTINCT;  // (a slot of the distinct pass: bits or counts)
     default: return ACC_HLL;
   }
 }
+
+// The functions the distinct pass answers (distinct.hip): a bitmap or a count per query-global dictionary id
+inline bool is_distinct_fn(int32_t f) { return f == PHIP_AGG_DISTINCT || f == PHIP_AGG_VALUE_COUNTS; }
+inline const char *distinct_fn_name(int32_t f) { return f == PHIP_AGG_DISTINCT ? "DISTINCTCOUNT" : "value counts (PERCENTILE / MODE)"; }
 
 }  // namespace
 
@@ -1995,10 +2000,12 @@ struct Plan {
   std::vector<std::vector<const void *>> sel_str_ptrs;  // per SEL_STR expression: its segments' bytes, then offsets
   std::vector<int32_t> sel_bits, sel_width;  // per select column's projected bytes (algorithmic bytes)
   float sel_filter_ms = 0.f;
-  // exact DISTINCTCOUNT (distinct.hip): slot s = the plan's s-th PHIP_AGG_DISTINCT aggregation (dist_agg[s]); the
+  // exact DISTINCTCOUNT and value counts (distinct.hip): slot s = the plan's s-th PHIP_AGG_DISTINCT or
+  // PHIP_AGG_VALUE_COUNTS aggregation (dist_agg[s]); the
   // descriptor in the blob, the bitmap [dense key space][row words] cleared and filled by every execution
   int ndist = 0;
   std::vector<int> dist_agg;
+  std::vector<int32_t> dist_kinds;  // per slot PHIP_DISTINCT_SLOT_*: bits (PHIP_AGG_DISTINCT) or counts (PHIP_AGG_VALUE_COUNTS)
   std::vector<std::shared_ptr<Device::Remap>> dist_dicts;
   DevDistinctQuery dstq{};
   size_t dstq_off = 0;
@@ -2341,14 +2348,21 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (ag.program < 0 || ag.program >= nprog)
       return fail(PHIP_ERR_INVALID, "aggregation %d: program %d outside [0, %d)", a, ag.program, nprog);
     d.program = ag.program;
-    if (ag.function < PHIP_AGG_COUNT || ag.function > PHIP_AGG_DISTINCT) return fail(PHIP_ERR_INVALID, "bad aggregation function");
-    if (ag.function == PHIP_AGG_DISTINCT) {  // the refusals of include/pinot_hip.h PHIP_AGG_DISTINCT
-      if (ag.expr != PHIP_EXPR_COLUMN) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT of an expression");
-      if (nprog > 1) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT beside several filter programs");
-      if (q->null_group_by) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT beside null group keys");
-      if (P.tuple_keys) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over a tuple key space");
-      if (tl_node_docs > 0) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT in a node plan");
-      if (want_bitmap || q->num_select > 0) return fail(PHIP_ERR_INVALID, "DISTINCTCOUNT outside an aggregation query");
+    if (ag.function < PHIP_AGG_COUNT || ag.function > PHIP_AGG_VALUE_COUNTS) return fail(PHIP_ERR_INVALID, "bad aggregation function");
+    if (is_distinct_fn(ag.function)) {  // the refusals of include/pinot_hip.h PHIP_AGG_DISTINCT / PHIP_AGG_VALUE_COUNTS
+      const char *fn = distinct_fn_name(ag.function);
+      if (ag.expr != PHIP_EXPR_COLUMN) return fail(PHIP_ERR_UNSUPPORTED, "%s of an expression", fn);
+      if (nprog > 1) return fail(PHIP_ERR_UNSUPPORTED, "%s beside several filter programs", fn);
+      if (q->null_group_by) return fail(PHIP_ERR_UNSUPPORTED, "%s beside null group keys", fn);
+      if (P.tuple_keys) return fail(PHIP_ERR_UNSUPPORTED, "%s over a tuple key space", fn);
+      if (tl_node_docs > 0) return fail(PHIP_ERR_UNSUPPORTED, "%s in a node plan", fn);
+      if (want_bitmap || q->num_select > 0) return fail(PHIP_ERR_INVALID, "%s outside an aggregation query", fn);
+    }
+    if (ag.function == PHIP_AGG_VALUE_COUNTS) {  // a u32 count per id: it must not wrap
+      int64_t docs = 0;
+      for (int s = 0; s < nseg; s++) docs += segs[s]->num_docs;
+      if (docs >= ((int64_t)1 << 32))
+        return fail(PHIP_ERR_UNSUPPORTED, "value counts (PERCENTILE / MODE) over %lld docs: a u32 count could wrap", (long long)docs);
     }
     if (ag.function != PHIP_AGG_COUNT) {
       if (ag.column_a < 0 || ag.column_a >= ncols) return fail(PHIP_ERR_INVALID, "aggregation column out of range");
@@ -2365,9 +2379,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       for (int s = 0; s < nseg; s++) {
         const ColumnStore &ca = segs[s]->cols[colidx[s][ag.column_a]];
         if (!(ca.type == PHIP_TYPE_INT || ca.type == PHIP_TYPE_LONG)) integral = false;
-        if (ag.function == PHIP_AGG_DISTINCT) {  // dictionary ids only: any type, but a dictionary in every segment
+        if (is_distinct_fn(ag.function)) {  // dictionary ids only: any type, but a dictionary in every segment
           if (no_dict(ca) || ca.fwd_kind == PHIP_FWD_HLL_REGISTERS || ca.words == nullptr)
-            return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over the raw (no-dictionary) column %s", ca.name.c_str());
+            return fail(PHIP_ERR_UNSUPPORTED, "%s over the raw (no-dictionary) column %s", distinct_fn_name(ag.function),
+                        ca.name.c_str());
+          if (ag.function == PHIP_AGG_VALUE_COUNTS && ca.type == PHIP_TYPE_STRING)  // (PERCENTILE / MODE are numeric)
+            return fail(PHIP_ERR_UNSUPPORTED, "value counts (PERCENTILE / MODE) over the STRING column %s", ca.name.c_str());
           continue;
         }
         if (ca.type == PHIP_TYPE_STRING && ag.function != PHIP_AGG_HLL)
@@ -2462,7 +2479,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         }
       }
       for (int a = 0; a < naggs; a++)
-        if (q->aggregations[a].function == PHIP_AGG_HLL || q->aggregations[a].function == PHIP_AGG_DISTINCT)
+        if (q->aggregations[a].function == PHIP_AGG_HLL || is_distinct_fn(q->aggregations[a].function))
           use_vals[q->aggregations[a].column_a] = false;  // (their ids / per-id entries are read)
       for (int k = 0; k < q->num_group_by; k++)
         if (q->group_by_columns[k] >= 0 && q->group_by_columns[k] < ncols) use_vals[q->group_by_columns[k]] = false;
@@ -2562,7 +2579,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     bool ok = dq.dense_batch != 0 && q->num_group_by == 0;
     for (int a = 0; a < naggs && ok; a++) {
       const phip_aggregation &ag = q->aggregations[a];
-      if (ag.function == PHIP_AGG_COUNT || ag.function == PHIP_AGG_DISTINCT) continue;  // (no value read in this walk)
+      if (ag.function == PHIP_AGG_COUNT || is_distinct_fn(ag.function)) continue;  // (no value read in this walk)
       for (int which = 0; which < 2; which++) {
         const int c = which == 0 ? ag.column_a : (ag.expr != PHIP_EXPR_COLUMN ? ag.column_b : -1);
         if (c < 0) continue;
@@ -2765,10 +2782,13 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   DevDistinctQuery dstq;
   memset(&dstq, 0, sizeof(dstq));
   if (!P.dist_agg.empty()) {
+    bool any_counts = false;
+    for (int a : P.dist_agg) any_counts |= q->aggregations[a].function == PHIP_AGG_VALUE_COUNTS;
+    const char *dn = any_counts ? "DISTINCTCOUNT / value counts" : "DISTINCTCOUNT";
     if (group_by && dq.mode == GB_HASH)
-      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over a hash-table group-by key space");
+      return fail(PHIP_ERR_UNSUPPORTED, "%s over a hash-table group-by key space", dn);
     for (const auto &gd : gb_dicts)
-      if (gd->raw || !gd->ids.empty()) return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over raw group-by keys");
+      if (gd->raw || !gd->ids.empty()) return fail(PHIP_ERR_UNSUPPORTED, "%s over raw group-by keys", dn);
     dstq.num_slots = (int32_t)P.dist_agg.size();
     dstq.num_rows = group_by ? dq.num_groups : 1;
     dstq.num_group_by = q->num_group_by;
@@ -2786,16 +2806,20 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         if (rc) return rc;
       }
       P.dist_dicts.push_back(col_remap[c]);
+      const bool counts = q->aggregations[P.dist_agg[s2]].function == PHIP_AGG_VALUE_COUNTS;
+      P.dist_kinds.push_back(counts ? PHIP_DISTINCT_SLOT_COUNTS : PHIP_DISTINCT_SLOT_BITS);
       dstq.slot_col[s2] = c;
       dstq.slot_card[s2] = col_remap[c]->card;
+      dstq.slot_kind[s2] = P.dist_kinds.back();
       dstq.slot_off[s2] = words;
-      words += ceil_div(std::max(col_remap[c]->card, 0), 32);
+      // a bit per query-global id, or a u32 count per id
+      words += counts ? std::max(col_remap[c]->card, 0) : ceil_div(std::max(col_remap[c]->card, 0), 32);
     }
     dstq.row_words = words;
     const char *mb = getenv("PHIP_DISTINCT_MAX_BYTES");
     const int64_t max_bytes = mb ? atoll(mb) : (int64_t)256 << 20;
     if ((long double)dstq.num_rows * (long double)words * 4 > (long double)max_bytes)
-      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT bitmaps of %lld rows x %lld words exceed PHIP_DISTINCT_MAX_BYTES %lld",
+      return fail(PHIP_ERR_UNSUPPORTED, "%s: %lld rows x %lld words exceed PHIP_DISTINCT_MAX_BYTES %lld", dn,
                   (long long)dstq.num_rows, (long long)words, (long long)max_bytes);
     // LDS regime: no group-by and every slot's words within the budget (default kDistinctLdsWords = 32 KiB per
     // workgroup: four workgroups stay resident per CU, and a flush is at most 8192 atomics per workgroup); clamped to
@@ -2803,6 +2827,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     const char *lw = getenv("PHIP_DISTINCT_LDS_WORDS");
     const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(lw ? atoll(lw) : kDistinctLdsWords, 12288));
     dstq.lds = (!group_by && words <= lds_words) ? 1 : 0;
+    // counts slots of a small dictionary in global rows: the lanes of a wave that share a word add once (distinct.hip).
+    // PHIP_COUNTS_COMBINE_CARD / PHIP_COUNTS_COMBINE_ROUNDS (environment, measurement overrides: tools/percentile_probe.py)
+    // = the largest such cardinality (0 = never) and the rounds of peeling
+    const char *cc = getenv("PHIP_COUNTS_COMBINE_CARD"), *cr = getenv("PHIP_COUNTS_COMBINE_ROUNDS");
+    dstq.combine_rounds = (int32_t)std::max<int64_t>(0, std::min<int64_t>(cr ? atoll(cr) : kCountsCombineRounds, 64));
+    dstq.combine_card = (int32_t)std::max<int64_t>(0, std::min<int64_t>(cc ? atoll(cc) : kCountsCombineCard, INT32_MAX));
   }
 
   // ---- staging blob: segments, nodes, leaf aux ------------------------------------------------
@@ -3205,7 +3235,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   }
   // (the re-size above may have turned a large dense key space into a hash table after the first check)
   if (!P.dist_agg.empty() && group_by && dq.mode == GB_HASH)
-    return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT over a hash-table group-by key space");
+    return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT / value counts over a hash-table group-by key space");
   dq.num_segs = (int32_t)dsegs.size();
   const size_t segs_off = blob.reserve(sizeof(DevSeg) * std::max<size_t>(dsegs.size(), 1));
 
@@ -4158,7 +4188,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     // accepted only when the dense key space fits trim_size: the trim can then never fire (groups <= key space), and
     // ordering is the broker reduce's job as for every untrimmed result.
     auto is_dist = [&](int32_t i) {
-      return i >= 0 && i < q->num_aggregations && q->aggregations[i].function == PHIP_AGG_DISTINCT;
+      return i >= 0 && i < q->num_aggregations && is_distinct_fn(q->aggregations[i].function);
     };
     bool on_distinct = false;
     if (q->num_order_terms > 0 && q->order_terms) {
@@ -4171,7 +4201,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       on_distinct = is_dist(q->order_by_aggregation);
     }
     if (on_distinct && gb_key_space > q->trim_size)  // (the dense key space itself, whatever the table's placement)
-      return fail(PHIP_ERR_UNSUPPORTED, "ORDER BY a DISTINCTCOUNT over a key space of %lld above trim_size %lld",
+      return fail(PHIP_ERR_UNSUPPORTED, "ORDER BY a DISTINCTCOUNT / value counts over a key space of %lld above trim_size %lld",
                   (long long)gb_key_space, (long long)q->trim_size);
   }
   P.total_work = total_work;
@@ -4741,7 +4771,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   Device *dev = P.dev;
   std::lock_guard<std::mutex> xlock(P.exec_mu);
   if (mode != EXEC_FULL && P.ndist > 0)
-    return fail(PHIP_ERR_UNSUPPORTED, "partial tables: a plan with a DISTINCTCOUNT has no mergeable table");
+    return fail(PHIP_ERR_UNSUPPORTED, "partial tables: a plan with a DISTINCTCOUNT or value counts has no mergeable table");
   // (a node part's hash table goes out too: node.cpp inserts the other parts' groups into the root's table)
   if (mode != EXEC_FULL && (!P.group_by || (P.dq.mode == GB_HASH && !P.node_part)))
     return fail(PHIP_ERR_UNSUPPORTED, "partial tables: dense group-by and aggregation plans only (this plan: %s)",
@@ -4980,7 +5010,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     // kept group's values come only from the segments that kept it. The distinct bitmaps hold one row per key over
     // every segment's docs, which is that answer for one segment only: with several the CPU plan maker answers.
     if (limit_pass && P.ndist > 0 && nseg > 1)
-      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT: %lld groups reach numGroupsLimit %lld over %d segments",
+      return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT / value counts: %lld groups reach numGroupsLimit %lld over %d segments",
                   (long long)ngroups, (long long)P.num_groups_limit, nseg);
     // the compacted keys, values, exact sums and registers of the groups back to back in one buffer (one copy out)
     auto contiguous_out = [&](const char *name, int64_t n, void **k, void **v, void **l, void **h) -> int32_t {
@@ -5220,6 +5250,8 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     r.num_distinct = P.ndist;
     r.distinct_words = impl->dist_words.data();
     r.distinct_word_offsets = impl->dist_offsets.data();
+    for (int s = 0; s < P.ndist; s++)  // bit s: slot s holds u32 counts (PHIP_AGG_VALUE_COUNTS), not bits
+      if (P.dist_kinds[s] == PHIP_DISTINCT_SLOT_COUNTS) r.reserved_distinct |= 1 << s;
     if (P.timed && !P.graph_exec) {
       float t_d = 0.f;
       HIP_TRY(hipEventElapsedTime(&t_d, P.dist_ev[0], P.dist_ev[1]));
@@ -5402,7 +5434,7 @@ static int32_t agg_partial_buffers(Plan &P) {
 static int32_t execute_agg_partial(Plan &P, phip_partial *part) {
   if (P.select || P.naggs > kMaxAggs) return fail(PHIP_ERR_UNSUPPORTED, "partial tables: not for selection plans");
   if (P.ndist > 0)
-    return fail(PHIP_ERR_UNSUPPORTED, "partial tables: a plan with a DISTINCTCOUNT has no mergeable table");
+    return fail(PHIP_ERR_UNSUPPORTED, "partial tables: a plan with a DISTINCTCOUNT or value counts has no mergeable table");
   phip_result *res = nullptr;
   int32_t rc = execute_plan(P, &res, nullptr, EXEC_FULL);  // (refuses while a partial is pending)
   if (rc) return rc;

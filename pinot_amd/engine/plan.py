@@ -32,8 +32,8 @@ from ..query.sql import parse
 from ..spi import (DEFAULT_GROUPBY_TRIM_THRESHOLD, DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE,
                    DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE, DEFAULT_NUM_GROUPS_LIMIT, MAX_TRIM_THRESHOLD, DataType)
 from .results import (AggregationResultsBlock, ExecutionStatistics, GroupByResultsBlock, SelectionResultsBlock,
-                      java_double_key,
-                      merge_intermediate)
+                      double_image_counts, java_double_key,
+                      merge_intermediate, value_counts)
 from .segment import GpuSegment
 
 
@@ -468,6 +468,15 @@ def plan_aggregations(aggs: Sequence[AggregationInfo], programs: Optional[Sequen
             if programs is not None:
                 raise UnsupportedOnGpu("distinctcount beside FILTER / CASE / null-handling filter programs")
             mapping.append((f, slot((_lib.AGG_DISTINCT,) + expr + (0,))))
+        elif f in ("percentile", "mode"):
+            # exact: one u32 count per query-global dictionary id of the column (PHIP_AGG_VALUE_COUNTS) -- the multiset
+            # of its values, which every percentile and every mode of that column is computed from, so they all share
+            # one primitive. The refusals are DISTINCTCOUNT's.
+            if expr[0] != _lib.EXPR_COLUMN:
+                raise UnsupportedOnGpu(f"{f} of an expression is not on the GPU path")
+            if programs is not None:
+                raise UnsupportedOnGpu(f"{f} beside FILTER / CASE / null-handling filter programs")
+            mapping.append((f, slot((_lib.AGG_VALUE_COUNTS,) + expr + (0,))))
         else:
             raise UnsupportedOnGpu(f"aggregation {f} is not on the GPU path")
     return prims, mapping
@@ -497,15 +506,29 @@ class GpuCombineOperator:
         self.prims, self.mapping = plan_aggregations(query.aggregations, programs[1] if programs is not None else None)
         nh = null_handling_enabled(query)
         for p in self.prims:
-            if p[0] != _lib.AGG_DISTINCT:
+            if p[0] not in (_lib.AGG_DISTINCT, _lib.AGG_VALUE_COUNTS):
                 continue
+            fn = "distinctcount" if p[0] == _lib.AGG_DISTINCT else "percentile / mode"
             if nh:
-                raise UnsupportedOnGpu("distinctcount with enableNullHandling")
+                raise UnsupportedOnGpu(f"{fn} with enableNullHandling")
             if segment_filters is not None:
-                raise UnsupportedOnGpu("distinctcount over a star-tree's documents")
+                raise UnsupportedOnGpu(f"{fn} over a star-tree's documents")
             for s in self.segments:
                 if s.has_column(p[2]) and not s.column_metadata(p[2]).has_dictionary:
-                    raise UnsupportedOnGpu(f"distinctcount over the raw (no-dictionary) column {p[2]}")
+                    raise UnsupportedOnGpu(f"{fn} over the raw (no-dictionary) column {p[2]}")
+                if p[0] == _lib.AGG_VALUE_COUNTS and s.has_column(p[2]) and \
+                        _STORED[s.column_metadata(p[2]).data_type] == "STRING":
+                    raise UnsupportedOnGpu(f"{fn} over the STRING column {p[2]}")
+        # MODE over a real column that holds NaN: the reference's tie-break between a NaN key and another of equal
+        # count follows its hash map's iteration order (every comparison with NaN is false), so there is no answer
+        # to match. The segments know (GpuSegment.real_specials: a sorted dictionary's last entry), as for
+        # _refuse_nan_extrema.
+        for ag in query.aggregations:
+            if ag.function == "mode" and isinstance(_strip_cast(ag.argument), Identifier):
+                c = _strip_cast(ag.argument).name
+                for s in self.segments:
+                    if s.has_column(c) and s.real_specials(c)[0]:
+                        raise UnsupportedOnGpu(f"mode over column {c}, which holds NaN in segment {s.name}")
         # enableNullHandling: the group-by columns whose null docs key as the null key (phip_query_desc.null_group_by;
         # NoDictionary*GroupKeyGenerator with null handling, DefaultGroupByExecutor.java:106-116)
         self.null_keys = 0
@@ -879,21 +902,30 @@ class GpuCombineOperator:
         return blk
 
     def _distinct_sets(self, lib, res, r, ng):
-        """{primitive index: [per group the set of the column's values]} of a result's DISTINCTCOUNT slots
-        (phip_result.distinct_words over phip_result_distinct_dictionary): slot s is the s-th AGG_DISTINCT primitive."""
+        """{primitive index: [per group the intermediate]} of a result's distinct slots (phip_result.distinct_words over
+        phip_result_distinct_dictionary): slot s is the s-th AGG_DISTINCT or AGG_VALUE_COUNTS primitive. A bits slot
+        (DISTINCTCOUNT) gives the set of the column's values, a counts slot (PERCENTILE / MODE) their {value: count}."""
         nd = int(r.num_distinct)
         offs = [int(r.distinct_word_offsets[i]) for i in range(nd + 1)]
         rw = offs[nd]
         words = (np.ctypeslib.as_array(r.distinct_words, shape=(ng * rw,)).reshape(ng, rw) if ng * rw
                  else np.zeros((ng, rw), np.uint32))
         out = {}
-        slots = [i for i, p in enumerate(self.prims) if p[0] == _lib.AGG_DISTINCT]
+        slots = [i for i, p in enumerate(self.prims) if p[0] in (_lib.AGG_DISTINCT, _lib.AGG_VALUE_COUNTS)]
         for s, i in enumerate(slots):
             dv = _lib.DictionaryView()
             _lib.check(lib.phip_result_distinct_dictionary(res, s, ctypes.byref(dv)))
+            counts = (int(r.reserved_distinct) >> s) & 1 == _lib.DISTINCT_SLOT_COUNTS
+            assert counts == (self.prims[i][0] == _lib.AGG_VALUE_COUNTS)
             w = np.ascontiguousarray(words[:, offs[s]:offs[s + 1]])
             if w.shape[1] == 0:
-                out[i] = [set() for _ in range(ng)]
+                out[i] = [dict() if counts else set() for _ in range(ng)]
+                continue
+            if counts:  # word j = the docs whose value is entry j of the dictionary
+                rows, ids = np.nonzero(w)
+                vals, nums = _dictionary_array(dv, ids), w[rows, ids]
+                cuts = np.searchsorted(rows, np.arange(ng + 1))
+                out[i] = [value_counts(vals[cuts[g]:cuts[g + 1]], nums[cuts[g]:cuts[g + 1]]) for g in range(ng)]
                 continue
             bits = np.unpackbits(w.view(np.uint8), axis=1, bitorder="little")  # bit i of word w = id 32 w + i
             rows, ids = np.nonzero(bits)
@@ -975,7 +1007,8 @@ class GpuCombineOperator:
                 hll = np.ctypeslib.as_array(r.hll_registers, shape=(ng * r.num_hll * m,)).reshape(ng, r.num_hll, m).copy()
             # long_exact[a]: the library kept an exact int64 sum (else it summed in double: int64 overflow bound)
             exact = [bool(r.long_exact[i]) for i in range(na)] if na else []
-            # DISTINCTCOUNT: per primitive the groups' value sets, from the bitmaps over the slot's dictionary
+            # DISTINCTCOUNT / PERCENTILE / MODE: per primitive the groups' value sets or value counts, over the slot's
+            # dictionary
             dsets = self._distinct_sets(lib, res, r, ng) if r.num_distinct else {}
 
             def prim_value(g, i):
@@ -986,7 +1019,7 @@ class GpuCombineOperator:
                     return int(longs[g][i]) if exact[i] else float(vals[g][i])
                 if f in (_lib.AGG_MIN, _lib.AGG_MAX):
                     return float(vals[g][i])
-                if f == _lib.AGG_DISTINCT:
+                if f in (_lib.AGG_DISTINCT, _lib.AGG_VALUE_COUNTS):
                     return dsets[i][g]
                 return hll[g, hll_slot[i], :1 << self.prims[i][4]].copy()  # (slots hold 2^max-log2m bytes)
 
@@ -995,6 +1028,8 @@ class GpuCombineOperator:
                 for f, s in self.mapping:
                     if f in ("avg", "minmaxrange"):
                         out.append((prim_value(g, s[0]), prim_value(g, s[1])))
+                    elif f == "percentile":  # (keyed by the values' double images; MODE keeps the stored type)
+                        out.append(double_image_counts(prim_value(g, s)))
                     else:
                         out.append(prim_value(g, s))
                 return out
@@ -1022,7 +1057,7 @@ class GpuCombineOperator:
                         prim_arrays.append(longs[:, i].copy())
                     elif f in (_lib.AGG_SUM, _lib.AGG_MIN, _lib.AGG_MAX):
                         prim_arrays.append(vals[:, i].copy())
-                    elif f == _lib.AGG_DISTINCT:
+                    elif f in (_lib.AGG_DISTINCT, _lib.AGG_VALUE_COUNTS):
                         col = np.empty(ng, dtype=object)
                         col[:] = dsets[i]
                         prim_arrays.append(col)
@@ -2308,9 +2343,9 @@ class GpuInstancePlanMaker:
             return st
         if query.is_selection:
             return GpuSelectionOperator(query, segments, limit)
-        if any(ag.function == "distinctcount" for ag in query.aggregations) and any(
+        if any(ag.function in ("distinctcount", "percentile", "mode") for ag in query.aggregations) and any(
                 ag.filter is not None or (ag.argument is not None and _is_case(ag.argument)) for ag in query.aggregations):
-            raise UnsupportedOnGpu("distinctcount in a query with FILTER clauses or CASE aggregations")
+            raise UnsupportedOnGpu("distinctcount / percentile / mode in a query with FILTER clauses or CASE aggregations")
         if any(ag.argument is not None and _is_case(ag.argument) for ag in query.aggregations):
             return GpuCaseAggregationOperator(query, segments, limit)
         if any(ag.filter is not None for ag in query.aggregations):

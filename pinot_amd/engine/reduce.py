@@ -14,7 +14,7 @@ from typing import List
 
 import numpy as np
 
-from ..query.context import FilterClause, Function, Identifier, Literal, QueryContext, SUPPORTED_AGGREGATIONS
+from ..query.context import FilterClause, Function, Identifier, Literal, QueryContext, aggregation_call
 from ..spi import DEFAULT_HYPERLOGLOG_LOG2M
 from .results import AggregationResultsBlock, ExecutionStatistics, GroupByResultsBlock, merge_intermediate
 
@@ -73,10 +73,52 @@ def order_key(ob, value):
     return key
 
 
-def final_result(function: str, v):
-    """AggregationFunction.extractFinalResult (a null intermediate stays null)."""
+def percentile_of_counts(counts, percentile: float) -> float:
+    """PercentileAggregationFunction.extractFinalResult (:155-172) over a {value: count} multiset instead of the sorted
+    value list: the list's element at index size - 1 when percentile == 100, else at (int) ((long) size * percentile /
+    100) -- a long times a double, truncated -- found by walking the values in Arrays.sort's order (Double.compare:
+    -0.0 below 0.0, NaN last) by cumulative count. Empty: -inf (DEFAULT_FINAL_RESULT)."""
+    size = sum(counts.values())
+    if size == 0:
+        return float("-inf")
+    index = size - 1 if percentile == 100 else int(float(size) * percentile / 100)
+    seen = 0
+    for v in sorted(counts, key=double_order):
+        seen += counts[v]
+        if index < seen:
+            return float(v)
+    raise AssertionError("index beyond the values")  # (index <= size - 1 for a percentile in [0, 100])
+
+
+def mode_of_counts(counts, reducer: str) -> float:
+    """ModeAggregationFunction.extractFinalResult (:501-707) over its {value: count} map: of the values of maximal
+    count the smallest (MIN), the largest (MAX) or their mean (AVG), as a double; empty: -inf. AVG sums in ascending
+    value order where the reference sums in its hash map's iteration order, so the last bits of a DOUBLE AVG over
+    several values may differ; MIN / MAX between a -0.0 and a 0.0 of equal count depend on that iteration order in the
+    reference (its comparison is the primitive <, which ties the zeros) and take Double.compare's order here."""
+    if not counts:
+        return float("-inf")
+    top = max(counts.values())
+    modes = sorted((v for v, n in counts.items() if n == top), key=order_value)
+    if reducer == "MIN":
+        return float(modes[0])
+    if reducer == "MAX":
+        return float(modes[-1])
+    total = 0.0
+    for v in modes:
+        total += float(v)
+    return total / len(modes)
+
+
+def final_result(function: str, v, agg=None):
+    """AggregationFunction.extractFinalResult (a null intermediate stays null). ``agg``: the AggregationInfo, which
+    PERCENTILE (its percentile) and MODE (its reducer) need beyond the function's name."""
     if v is None:
         return None
+    if function == "percentile":
+        return percentile_of_counts(v, agg.percentile)
+    if function == "mode":
+        return mode_of_counts(v, agg.reducer)
     if function == "count":
         return int(v)
     if function == "sum":
@@ -109,8 +151,16 @@ def _agg_index(query: QueryContext, expr):
         expr, flt = expr.function, expr.filter
     if not isinstance(expr, Function):
         return None
+    try:
+        call = aggregation_call(expr)
+    except ValueError:
+        call = None
+    if call is None:
+        return None
+    name, extras = call[0], call[1:]  # (percentile, version, reducer: they tell two PERCENTILEs of one column apart)
     for i, a in enumerate(query.aggregations):  # exact argument first (COUNT(col) under enableNullHandling)
-        if expr.name == a.function and a.filter == flt and expr.args and expr.args[0] == a.argument:
+        if name == a.function and a.filter == flt and expr.args and expr.args[0] == a.argument and \
+                extras == (a.percentile, a.version, a.reducer):
             return i
     for i, a in enumerate(query.aggregations):
         if expr.name == a.function == "count" and a.filter == flt and a.argument is None:
@@ -126,6 +176,10 @@ def _column_name(expr, alias, query=None):
         if i is not None and query.aggregations[i].argument is not None:
             return f"count({query.aggregations[i].argument})"  # (enableNullHandling: CountAggregationFunction.java:64-66)
         return "count(*)"
+    if isinstance(expr, Function) and query is not None and expr.name.startswith("percentile"):
+        i = _agg_index(query, expr)
+        if i is not None:  # (percentile(col, 95.0): PercentileAggregationFunction.getResultColumnName)
+            return query.aggregations[i].result_column_name
     return str(expr)
 
 
@@ -143,7 +197,7 @@ def reduce_blocks(query: QueryContext, blocks) -> ResultTable:
                 merged = list(b.results)
             else:
                 merged = [merge_intermediate(a.function, x, y) for a, x, y in zip(query.aggregations, merged, b.results)]
-        finals = [final_result(a.function, v) for a, v in zip(query.aggregations, merged)]
+        finals = [final_result(a.function, v, a) for a, v in zip(query.aggregations, merged)]
         row = []
         for e, _ in query.select:
             i = _agg_index(query, e)
@@ -164,7 +218,7 @@ def reduce_blocks(query: QueryContext, blocks) -> ResultTable:
     gb_index = {str(e): i for i, e in enumerate(query.group_by)}
     records = []
     for k, v in groups.items():
-        finals = [final_result(a.function, x) for a, x in zip(query.aggregations, v)]
+        finals = [final_result(a.function, x, a) for a, x in zip(query.aggregations, v)]
         records.append((k, finals))
 
     def value_of(expr, rec):
@@ -225,7 +279,7 @@ def trim_groups(query: QueryContext, block, min_trim=None):
     if not k or len(block.groups) <= k:
         return block
     gb_index = {str(e): i for i, e in enumerate(query.group_by)}
-    recs = [(key, [final_result(a.function, x) for a, x in zip(query.aggregations, v)]) for key, v in block.groups.items()]
+    recs = [(key, [final_result(a.function, x, a) for a, x in zip(query.aggregations, v)]) for key, v in block.groups.items()]
     recs.sort(key=lambda r: tuple((x is None, order_value(x)) for x in r[0]))  # (a null key after the values)
 
     def value_of(expr, rec):

@@ -8,7 +8,9 @@
 Intermediate results follow each function's intermediate type:
   count -> int, sum -> float (int when every input is INT/LONG: exact), min/max ->
   float, avg -> (sum, count), minmaxrange -> (min, max), distinctcounthll -> uint8 registers,
-  distinctcount -> set of the column's values (FLOAT / DOUBLE members keyed by their bits: java_double_key).
+  distinctcount -> set of the column's values (FLOAT / DOUBLE members keyed by their bits: java_double_key),
+  percentile / mode -> {value: count}, the exact multiset of the column's values (value_counts): PERCENTILE keys by
+  the values' double images (the reference's DoubleArrayList), MODE by the stored type (its typed value -> count map).
 """
 import math
 from dataclasses import dataclass, field
@@ -120,7 +122,8 @@ class GroupByResultsBlock:
         if name != "groups" or "prim_columns" not in self.__dict__:
             raise AttributeError(name)
         prim = [[row.copy() for row in c] if c.ndim == 2 else c.tolist() for c in self.prim_columns]
-        fcols = [list(zip(prim[sl[0]], prim[sl[1]])) if fn in ("avg", "minmaxrange") else prim[sl]
+        fcols = [list(zip(prim[sl[0]], prim[sl[1]])) if fn in ("avg", "minmaxrange") else
+                 ([double_image_counts(m) for m in prim[sl]] if fn == "percentile" else prim[sl])
                  for fn, sl in self._mapping]
         kt = self.__dict__.get("key_types") or [None] * len(self.key_columns)
         cols = [key_column_list(c, t) for c, t in zip(self.key_columns, kt)]
@@ -154,6 +157,30 @@ class SelectionResultsBlock:
         return [list(r) for r in zip(*cols)] if cols else []
 
 
+def value_counts(values, counts):
+    """A MODE intermediate: {value: count} of the parallel arrays `values` (a numeric numpy array in the column's
+    stored type) and `counts`, entries of count 0 left out. INT / LONG keys are ints; real keys are floats (a FLOAT as
+    its double image) that compare by their bits (java_double_key): -0.0 and 0.0 are two keys, every NaN is one."""
+    out = {}
+    for v, n in zip(np.asarray(values).tolist(), np.asarray(counts).tolist()):
+        if n:
+            k = java_double_key(v)
+            out[k] = out.get(k, 0) + n
+    return out
+
+
+def double_image_counts(counts):
+    """A PERCENTILE intermediate from a MODE one: keys are the values' double images (the reference collects
+    getDoubleValuesSV() into a DoubleArrayList), so two LONGs with one image add their counts."""
+    if all(isinstance(k, float) for k in counts):
+        return counts
+    out = {}
+    for v, n in counts.items():
+        k = java_double_key(float(v))
+        out[k] = out.get(k, 0) + n
+    return out
+
+
 def merge_intermediate(function: str, a, b):
     """AggregationFunction.merge for the functions on the path. None is a null intermediate result (enableNullHandling:
     no non-null value aggregated); merging it keeps the other side (SumAggregationFunction.merge under null handling,
@@ -181,4 +208,9 @@ def merge_intermediate(function: str, a, b):
         return np.maximum(a, b)
     if function == "distinctcount":  # value sets (BaseDistinctAggregateAggregationFunction.merge: addAll)
         return a | b
+    if function in ("percentile", "mode"):  # (DoubleArrayList.addAll / the value -> count maps' merge: counts add)
+        out = dict(a)
+        for k, n in b.items():
+            out[k] = out.get(k, 0) + n
+        return out
     raise NotImplementedError(function)

@@ -9,6 +9,7 @@ inputs to the hot path, not rebuilt):
   QueryContext           pinot-core/.../query/request/context/QueryContext.java:74-757
 """
 from dataclasses import dataclass, field
+from decimal import Decimal
 from typing import List, Optional, Tuple, Union
 
 
@@ -136,7 +137,66 @@ class FilterContext:
 
 # ----------------------------------------------------------------------------- aggregations
 SUPPORTED_AGGREGATIONS = ("count", "sum", "min", "max", "avg", "minmaxrange", "distinctcounthll",
-                          "distinctcountrawhll", "distinctcount")
+                          "distinctcountrawhll", "distinctcount", "percentile", "mode")
+
+MODE_REDUCERS = ("MIN", "MAX", "AVG")  # ModeAggregationFunction.MultiModeReducerType
+
+
+def java_double_string(v: float) -> str:
+    """Double.toString of a percentile ([0, 100]): the shortest digits that round-trip, as Python's repr, but in
+    computerised scientific notation below 1e-3 ('1.0E-4' where Python writes '0.0001')."""
+    v = float(v)
+    if v == 0.0 or abs(v) >= 1e-3:
+        return repr(v)
+    _, digits, exp = Decimal(repr(v)).as_tuple()
+    rest = "".join(map(str, digits[1:])) or "0"
+    return f"{digits[0]}.{rest}E{exp + len(digits) - 1}"
+
+
+def aggregation_function_of(name: str):
+    """A SQL function name -> (canonical aggregation function, percentile or None): PERCENTILEnn is PERCENTILE with
+    the integer nn in its name (AggregationFunctionFactory: the name's remainder parsed as the percentile)."""
+    if name in SUPPORTED_AGGREGATIONS:
+        return name, None
+    if name.startswith("percentile") and name[len("percentile"):].isdigit():
+        return "percentile", int(name[len("percentile"):])
+    return None, None
+
+
+def aggregation_call(fn: "Function"):
+    """(function, percentile, version, reducer) of an aggregation call, None for another function. PERCENTILE(col, p)
+    takes p as a number or a quoted one (AggregationFunctionFactory parses the literal's string); MODE(col[, 'MIN' |
+    'MAX' | 'AVG']). A percentile outside [0, 100], a reducer outside the three and a wrong argument count raise
+    ValueError."""
+    function, nn = aggregation_function_of(fn.name)
+    if function is None:
+        return None
+    if function == "percentile":
+        if nn is not None:
+            if len(fn.args) != 1:
+                raise ValueError(f"{fn.name} takes one argument")
+            p, version = float(nn), 0
+        else:
+            if len(fn.args) != 2 or not isinstance(fn.args[1], Literal):
+                raise ValueError("PERCENTILE takes a column and a literal percentile")
+            try:
+                p, version = float(fn.args[1].value), 1
+            except (TypeError, ValueError):
+                raise ValueError(f"PERCENTILE: {fn.args[1].value!r} is not a number") from None
+        if not 0.0 <= p <= 100.0:  # (NaN fails both comparisons)
+            raise ValueError(f"percentile {p} outside [0, 100]")
+        return function, p, version, "MIN"
+    if function == "mode":
+        if not 1 <= len(fn.args) <= 2:
+            raise ValueError("MODE takes a column and an optional reducer")
+        reducer = "MIN"
+        if len(fn.args) == 2:
+            r = fn.args[1]
+            if not isinstance(r, Literal) or r.value not in MODE_REDUCERS:  # (MultiModeReducerType.valueOf: exact case)
+                raise ValueError(f"MODE reducer {r} is not one of 'MIN', 'MAX', 'AVG'")
+            reducer = r.value
+        return function, None, 0, reducer
+    return function, None, 0, "MIN"
 
 
 @dataclass(frozen=True)
@@ -145,19 +205,27 @@ class AggregationInfo:
     argument: Optional[Expression]  # None for COUNT(*)
     log2m: int = 8
     filter: Optional["FilterContext"] = None  # FILTER(WHERE ...) of a filtered aggregation
+    percentile: Optional[float] = None  # PERCENTILE: the percentile, in [0, 100]
+    version: int = 0        # PERCENTILE: 0 = PERCENTILEnn(col), 1 = PERCENTILE(col, p) (PercentileAggregationFunction._version)
+    reducer: str = "MIN"    # MODE: what becomes of several values of maximal count (MODE_REDUCERS)
 
     @property
     def result_column_name(self) -> str:
         """AggregationFunction.getResultColumnName(): lower-case function name + argument; COUNT(col) keeps its
-        argument only under enableNullHandling (the argument is then set: CountAggregationFunction.java:44-66)."""
+        argument only under enableNullHandling (the argument is then set: CountAggregationFunction.java:44-66);
+        PERCENTILE names its percentile (PercentileAggregationFunction.java:60-64)."""
         if self.function == "count":
             base = "count(*)" if self.argument is None else f"count({self.argument})"
+        elif self.function == "percentile":
+            base = (f"percentile{int(self.percentile)}({self.argument})" if self.version == 0
+                    else f"percentile({self.argument}, {java_double_string(self.percentile)})")
         else:
             base = f"{self.function}({self.argument})"
         return base if self.filter is None else f"{base} FILTER(WHERE {self.filter})"
 
     def unfiltered(self) -> "AggregationInfo":
-        return AggregationInfo(self.function, self.argument, self.log2m)
+        return AggregationInfo(self.function, self.argument, self.log2m, None, self.percentile, self.version,
+                               self.reducer)
 
 
 @dataclass

@@ -11,7 +11,7 @@ expressions. The reference optimizer's flattening of nested AND/OR
 import re
 
 from .context import (AggregationInfo, FilterClause, FilterContext, Function, Identifier, Literal, OrderByExpression,
-                      Predicate, PredicateType, QueryContext, SUPPORTED_AGGREGATIONS, UNBOUNDED)
+                      Predicate, PredicateType, QueryContext, UNBOUNDED, aggregation_call, aggregation_function_of)
 
 _TOKEN = re.compile(r"""\s*(?:
     (?P<num>\d+\.\d*(?:[eE][-+]?\d+)?|\d+(?:[eE][-+]?\d+)?|\.\d+)
@@ -304,7 +304,7 @@ class _Parser:
         e = self.expr()
         if self.peek()[0] == "ident" and str(self.peek()[1]).lower() == "filter":
             # agg(...) FILTER(WHERE ...) (CalciteSqlParser's FILTER clause -> filtered aggregation)
-            if not (isinstance(e, Function) and e.name in SUPPORTED_AGGREGATIONS):
+            if not (isinstance(e, Function) and _is_aggregation(e)):
                 raise SqlError("FILTER applies to an aggregation")
             self.next()
             self.expect("op", "(")
@@ -337,12 +337,21 @@ class _Parser:
         return OrderByExpression(e, asc, nulls_last)
 
 
+def _is_aggregation(fn):
+    """An aggregation call: a supported function's name, PERCENTILEnn included."""
+    return aggregation_function_of(fn.name)[0] is not None
+
+
 def _collect_aggs(expr, out, flt=None, null_handling=False):
     if isinstance(expr, FilterClause):
         _collect_aggs(expr.function, out, expr.filter, null_handling)
         return
     if isinstance(expr, Function):
-        if expr.name in SUPPORTED_AGGREGATIONS:
+        if _is_aggregation(expr):
+            try:
+                function, percentile, version, reducer = aggregation_call(expr)
+            except ValueError as e:
+                raise SqlError(str(e)) from None
             arg = None
             if expr.name == "count":
                 # COUNT(col) counts the non-null values under enableNullHandling (an identifier or a function
@@ -357,7 +366,7 @@ def _collect_aggs(expr, out, flt=None, null_handling=False):
             log2m = 8
             if expr.name in ("distinctcounthll", "distinctcountrawhll") and len(expr.args) > 1:
                 log2m = int(expr.args[1].value)
-            info = AggregationInfo(expr.name, arg, log2m, flt)
+            info = AggregationInfo(function, arg, log2m, flt, percentile, version, reducer)
             if info not in out:
                 out.append(info)
             return
@@ -406,7 +415,7 @@ def parse(sql: str) -> QueryContext:
     for e, _ in select:
         if isinstance(e, FilterClause):
             continue
-        if not isinstance(e, Function) or e.name not in SUPPORTED_AGGREGATIONS:
+        if not isinstance(e, Function) or not _is_aggregation(e):
             if group_by and e not in group_by:
                 raise SqlError(f"select expression {e} is neither an aggregation nor a group-by expression")
     if not aggs and not group_by:
