@@ -216,10 +216,53 @@ typedef struct phip_filter_node {
 #define PHIP_EXPR_SUB 2    /* a - b   (SubtractionTransformFunction.java:99-124) */
 #define PHIP_EXPR_MUL 3    /* a * b   (MultiplicationTransformFunction.java:90-106) */
 
+/* ---- derived value columns: arbitrary arithmetic in aggregation arguments ----------------------------------
+ * An aggregation argument wider than the two-operand forms above -- a * (1 - b) * (1 + c), a * b / 100, a + b + c --
+ * is a postfix program over the query's columns and numeric literals, the chain of double transform functions the
+ * reference evaluates it with (pinot-core/.../operator/transform/function/AdditionTransformFunction.java,
+ * SubtractionTransformFunction.java, MultiplicationTransformFunction.java, DivisionTransformFunction.java and
+ * LiteralTransformFunction.java). The library evaluates the program once per segment into a doc-order value column
+ * (expr.hip), keeps it with the segment and reads it like any raw column: phip_query_desc.derived[k] is column index
+ * num_columns + k, valid only as column_a of a PHIP_AGG_SUM / MIN / MAX / HLL aggregation with expr ==
+ * PHIP_EXPR_COLUMN (any other use -- a group-by column, a filter leaf, a select expression, PHIP_AGG_DISTINCT /
+ * PHIP_AGG_VALUE_COUNTS -- is PHIP_ERR_INVALID). Every operation is one separately rounded IEEE binary64 operation
+ * (no fused multiply-add), as Java computes it. A SUM reads an exact int64 image instead when every leaf is an INT /
+ * LONG column or a PUSH_LONG, no DIV occurs, the value ranges of the segments' columns bound every intermediate below
+ * 2^62 and the whole sum below 2^58 (long_exact = 1 then). MIN, MAX and DISTINCTCOUNTHLL always read doubles.
+ * Limits (PHIP_ERR_UNSUPPORTED past them): PHIP_EXPR_MAX_OPS ops, a stack of PHIP_EXPR_MAX_STACK values,
+ * PHIP_EXPR_MAX_COLUMNS distinct columns per program; num_columns + the derived columns' value kinds <= 16; STRING
+ * and HLL-register operands; PHIP_DERIVED_MAX_BYTES (environment, per device, default 64 GiB) of derived columns all
+ * pinned by live plans; a library without the kernel. A malformed program is PHIP_ERR_INVALID. A segment keeps its 16
+ * most recently used derived columns; a plan keeps the ones it reads alive until phip_plan_destroy.
+ * num_entries_scanned_post_filter counts a program's distinct columns, as the reference's projection does. */
+#define PHIP_EXPR_OP_PUSH_COLUMN 0 /* push columns[column] of the doc */
+#define PHIP_EXPR_OP_PUSH_LONG 1   /* push long_value */
+#define PHIP_EXPR_OP_PUSH_DOUBLE 2 /* push double_value */
+#define PHIP_EXPR_OP_ADD 3         /* pop b, pop a, push a + b */
+#define PHIP_EXPR_OP_SUB 4         /* ... a - b */
+#define PHIP_EXPR_OP_MUL 5         /* ... a * b */
+#define PHIP_EXPR_OP_DIV 6         /* ... a / b */
+#define PHIP_EXPR_MAX_OPS 32
+#define PHIP_EXPR_MAX_STACK 8
+#define PHIP_EXPR_MAX_COLUMNS 8
+
+typedef struct phip_expr_op {
+  int32_t op;     /* PHIP_EXPR_OP_* */
+  int32_t column; /* PUSH_COLUMN: index into phip_query_desc.columns */
+  int64_t long_value;
+  double double_value;
+} phip_expr_op;
+
+typedef struct phip_derived_column {
+  const phip_expr_op *ops;
+  int32_t num_ops;
+  int32_t reserved;
+} phip_derived_column;
+
 typedef struct phip_aggregation {
   int32_t function; /* PHIP_AGG_* */
   int32_t expr;     /* PHIP_EXPR_* (ignored for COUNT) */
-  int32_t column_a; /* index into phip_query_desc.columns */
+  int32_t column_a; /* index into phip_query_desc.columns; num_columns + k = derived column k (PHIP_EXPR_COLUMN only) */
   int32_t column_b;
   int32_t log2m; /* HLL */
   int32_t program; /* filter program whose docs this aggregation reads (0 unless num_filter_programs > 1) */
@@ -284,6 +327,10 @@ typedef struct phip_query_desc {
   uint32_t stats_programs;
   const struct phip_select_expr *select;
   int64_t select_limit;
+  /* Derived value columns (see phip_expr_op above): derived[k] is column index num_columns + k. 0 / NULL = none. */
+  int32_t num_derived;
+  int32_t reserved_derived;
+  const phip_derived_column *derived;
 } phip_query_desc;
 
 typedef struct phip_select_expr {
@@ -406,6 +453,11 @@ PHIP_API int32_t phip_runtime_versions(int32_t *out_built, int32_t *out_runtime)
 PHIP_API int32_t phip_segment_load(const phip_segment_desc *desc, uint64_t *out_handle);
 PHIP_API int32_t phip_segment_unload(uint64_t handle);
 PHIP_API int32_t phip_segment_device_bytes(uint64_t handle, uint64_t *out_bytes);
+/* The segment's derived value columns (phip_query_desc.derived): how many it holds now (at most 16), their bytes, and
+ * the materialise launches since load -- a plan whose expression the segment already holds launches none.
+ * phip_segment_device_bytes stays what the segment's load pinned: it does not include these bytes (nor the other
+ * first-use derivatives), which come and go with the queries; a cache sized against device memory adds out_bytes. */
+PHIP_API int32_t phip_segment_derived_info(uint64_t handle, int32_t *out_count, int64_t *out_bytes, int64_t *out_builds);
 
 PHIP_API int32_t phip_query(const phip_query_desc *query, phip_result **out_result);
 

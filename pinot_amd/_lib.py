@@ -34,6 +34,9 @@ class RawRange(ctypes.Structure):
 AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_HLL, AGG_DISTINCT, AGG_VALUE_COUNTS = range(7)
 DISTINCT_SLOT_BITS, DISTINCT_SLOT_COUNTS = range(2)  # bit s of phip_result.reserved_distinct: slot s's kind
 EXPR_COLUMN, EXPR_ADD, EXPR_SUB, EXPR_MUL = range(4)
+# phip_expr_op codes and limits of a derived value column's postfix program (include/pinot_hip.h PHIP_EXPR_OP_*)
+EXPR_OP_PUSH_COLUMN, EXPR_OP_PUSH_LONG, EXPR_OP_PUSH_DOUBLE, EXPR_OP_ADD, EXPR_OP_SUB, EXPR_OP_MUL, EXPR_OP_DIV = range(7)
+EXPR_MAX_OPS, EXPR_MAX_STACK, EXPR_MAX_COLUMNS = 32, 8, 8
 
 EXPORTED_SYMBOLS = (
     "phip_init", "phip_shutdown", "phip_device_count", "phip_last_error", "phip_version",
@@ -42,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "phip_plan_destroy", "phip_global_dictionary", "phip_plan_execute_partial", "phip_plan_finish",
     "phip_runtime_versions", "phip_plan_abandon_partial", "phip_result_select_dictionary",
     "phip_plan_set_deadline", "phip_plan_cancel", "phip_plan_exchange", "phip_result_distinct_dictionary",
-    "phip_plan_launch_shape",
+    "phip_plan_launch_shape", "phip_segment_derived_info",
 )
 
 # phip_plan_exchange kinds (include/pinot_hip.h "node plans")
@@ -99,6 +102,16 @@ class SelectExpr(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class ExprOp(ctypes.Structure):
+    """phip_expr_op: one op of a derived value column's postfix program."""
+    _fields_ = [("op", ctypes.c_int32), ("column", ctypes.c_int32), ("long_value", ctypes.c_int64),
+                ("double_value", ctypes.c_double)]
+
+
+class DerivedColumn(ctypes.Structure):
+    _fields_ = [("ops", ctypes.POINTER(ExprOp)), ("num_ops", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class QueryDesc(ctypes.Structure):
     _fields_ = [("num_columns", ctypes.c_int32), ("num_segments", ctypes.c_int32),
                 ("columns", ctypes.POINTER(ctypes.c_char_p)), ("segments", ctypes.POINTER(ctypes.c_uint64)),
@@ -112,7 +125,9 @@ class QueryDesc(ctypes.Structure):
                 ("num_order_terms", ctypes.c_int32), ("num_filter_programs", ctypes.c_int32),
                 ("order_terms", ctypes.POINTER(OrderTerm)),
                 ("num_select", ctypes.c_int32), ("stats_programs", ctypes.c_uint32),
-                ("select", ctypes.POINTER(SelectExpr)), ("select_limit", ctypes.c_int64)]
+                ("select", ctypes.POINTER(SelectExpr)), ("select_limit", ctypes.c_int64),
+                ("num_derived", ctypes.c_int32), ("reserved_derived", ctypes.c_int32),
+                ("derived", ctypes.POINTER(DerivedColumn))]
 
 
 class Result(ctypes.Structure):
@@ -234,6 +249,8 @@ def load(with_torch: bool = False):
     lib.phip_segment_unload.restype = i32
     lib.phip_segment_device_bytes.argtypes = [u64, ctypes.POINTER(u64)]
     lib.phip_segment_device_bytes.restype = i32
+    lib.phip_segment_derived_info.argtypes = [u64, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.phip_segment_derived_info.restype = i32
     lib.phip_query.argtypes = [ctypes.POINTER(QueryDesc), ctypes.POINTER(ctypes.POINTER(Result))]
     lib.phip_query.restype = i32
     lib.phip_result_dictionary.argtypes = [ctypes.POINTER(Result), i32, ctypes.POINTER(DictionaryView)]

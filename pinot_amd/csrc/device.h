@@ -134,6 +134,27 @@ struct DevCol {
 };
 constexpr int kBitSliceMaxBits = 12;
 
+// A derived value column's program over one segment (expr.hip expr_materialize_kernel; include/pinot_hip.h
+// phip_expr_op): postfix, the limits of PHIP_EXPR_MAX_*. The host resolves every pushed column to the segment's own
+// column (cols[op.col]) and gives a constant in both images, so the double and the int64 instantiation read one layout.
+constexpr int kExprMaxOps = 32;
+constexpr int kExprMaxStack = 8;
+constexpr int kExprMaxCols = 8;
+constexpr int kMaxDerivedPerSegment = 16;  // derived columns a segment keeps (least recently used evicted)
+enum ExprOp : int32_t { EXOP_COLUMN = 0, EXOP_CONST = 1, EXOP_ADD = 2, EXOP_SUB = 3, EXOP_MUL = 4, EXOP_DIV = 5 };
+struct DevExprOp {
+  int32_t op;   // ExprOp
+  int32_t col;  // EXOP_COLUMN: index into DevExpr.cols
+  int64_t lval; // EXOP_CONST, int64 instantiation
+  double dval;  // EXOP_CONST, double instantiation
+};
+struct DevExpr {
+  int32_t num_ops;
+  int32_t num_docs;
+  DevExprOp ops[kExprMaxOps];
+  DevCol cols[kExprMaxCols];
+};
+
 // One group-by column's key id source for the tuple packing of key spaces above 2^62 (keys.hip tuple_words_kernel).
 constexpr int kMaxTupleCols = 8;
 constexpr int kMaxTupleWords = 4;

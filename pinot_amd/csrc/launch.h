@@ -133,6 +133,14 @@ hipError_t launch_distinct_mark(const DevDistinctQuery *q, int64_t total_work, i
 hipError_t launch_distinct_finish(const DevDistinctQuery *q, const int64_t *keys, int64_t num_out, int64_t *counts,
                                   uint32_t *out, hipStream_t s);
 
+// ---- expr.hip (derived value columns) ----------------------------------------------------------------------------
+// Not a launcher the runtime calls by name: the host simulation's stand-ins define every launcher above and nothing
+// else, so the runtime holds a pointer of this type (null by default: a query with derived columns is then
+// PHIP_ERR_UNSUPPORTED) and expr.hip registers its launcher from a static initialiser. e: the program in device
+// memory; out: num_docs values, double or (integral) int64_t.
+typedef hipError_t (*ExprLauncher)(const DevExpr *e, int32_t num_docs, bool integral, void *out, hipStream_t s);
+void register_expr_launcher(ExprLauncher f);  // defined in runtime.cpp
+
 // ---- keys.hip ----------------------------------------------------------------------------------------------------
 hipError_t set_str_hash_bits(int bits);
 hipError_t launch_raw_images(const void *raw, int32_t type, int64_t n, uint64_t *out, hipStream_t s);

@@ -311,6 +311,23 @@ static inline bool no_dict(const ColumnStore &c) {
 constexpr int kMaxRecordDevices = 64;
 static std::atomic<uint64_t> g_record_bytes[kMaxRecordDevices];
 
+// HBM held by derived value columns per device (ensure_derived's budget), and one column's values: freed when the
+// segment has evicted or dropped it and no plan reads it any more.
+static std::atomic<uint64_t> g_derived_bytes[kMaxRecordDevices];
+struct DerivedBuf {
+  void *p = nullptr;
+  uint64_t bytes = 0;
+  int device = 0;
+  ~DerivedBuf() {
+    if (device >= 0 && device < kMaxRecordDevices) g_derived_bytes[device] -= bytes;
+    (void)hipSetDevice(device);
+    if (p) (void)hipFree(p);
+  }
+};
+// expr.hip's launcher (launch.h ExprLauncher): null in a library without the kernel unit (the host simulation)
+static phip::ExprLauncher g_expr_launcher = nullptr;
+static std::atomic<uint64_t> g_derived_clock{0};  // last-use stamps of the derived columns (least recently used first out)
+
 struct Segment {
   uint64_t handle = 0;
   int device = 0;
@@ -327,6 +344,18 @@ struct Segment {
   };
   std::map<std::string, Record> records;
   uint64_t record_bytes = 0;
+  // Derived value columns (phip_query_desc.derived; ensure_derived): each takes one of kMaxDerivedPerSegment column
+  // slots behind the loaded columns (cols[base_cols + slot]; capacity reserved at load, so `cols` never moves), keyed
+  // by its canonical program and value kind. Guarded by the device's mutex like `records` and the doc-order values.
+  struct Derived {
+    std::string key;
+    int slot = 0;
+    uint64_t last_use = 0;
+    std::shared_ptr<DerivedBuf> buf;  // shared with the plans that read it: an evicted column lives on until they go
+  };
+  std::vector<Derived> derived;
+  int base_cols = 0;
+  int64_t derived_builds = 0;  // materialise launches since load (phip_segment_derived_info)
   ~Segment() {
     if (device >= 0 && device < kMaxRecordDevices) g_record_bytes[device] -= record_bytes;
     (void)hipSetDevice(device);
@@ -1880,6 +1909,7 @@ struct Plan {
   std::atomic<int64_t> deadline_ms{0};  // phip_plan_set_deadline (0 = none)
   std::atomic<int32_t> cancelled{0};    // phip_plan_cancel (sticky)
   std::vector<std::shared_ptr<Segment>> segs;  // keeps the segments' HBM alive while the plan exists
+  std::vector<std::shared_ptr<DerivedBuf>> derived_bufs;  // ... and the derived value columns it reads (ensure_derived)
   std::vector<void *> allocs;
   int32_t alloc(size_t bytes, void **out) {
     void *p = nullptr;
@@ -1918,6 +1948,7 @@ struct Plan {
   std::vector<int32_t> tuple_cols;  // the query's group-by columns
   int nseg = 0, naggs = 0, nhll = 0, log2m = 0, m_regs = 0, num_group_by = 0, num_projected = 0;
   int nprog = 1;   // filter programs (phip_query_desc.num_filter_programs)
+  std::vector<int> prog_projected;  // per program: the distinct columns its functions project (entries post filter)
   int nmatch = 0;  // seg_matched slots = nprog * nseg
   std::vector<int64_t> slot_docs;  // per seg_matched slot: the docs of that (program, segment) entry, 0 = pruned
   int64_t num_groups_limit = 0, total_work = 0, total_docs = 0, docs_in_work = 0;
@@ -2238,6 +2269,296 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
   return PHIP_OK;
 }
 
+// ================================================================================================
+// derived value columns (include/pinot_hip.h phip_expr_op; expr.hip)
+// ================================================================================================
+void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
+
+namespace {
+
+// One derived column's program, checked: well-formed postfix within the limits; its distinct query columns in
+// first-push order.
+struct ExprInfo {
+  std::vector<int> cols;
+  bool has_div = false, all_long = true;  // all_long: no PUSH_DOUBLE (the columns' types are per segment)
+};
+
+int32_t check_expr_program(const phip_query_desc *q, int k, ExprInfo &info) {
+  const phip_derived_column &d = q->derived[k];
+  if (d.num_ops <= 0 || !d.ops) return fail(PHIP_ERR_INVALID, "derived column %d: empty program", k);
+  if (d.num_ops > PHIP_EXPR_MAX_OPS)
+    return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: %d ops, at most %d", k, d.num_ops, PHIP_EXPR_MAX_OPS);
+  int depth = 0;
+  for (int i = 0; i < d.num_ops; i++) {
+    const phip_expr_op &o = d.ops[i];
+    switch (o.op) {
+      case PHIP_EXPR_OP_PUSH_COLUMN:
+        if (o.column < 0 || o.column >= q->num_columns)
+          return fail(PHIP_ERR_INVALID, "derived column %d: op %d pushes column %d, outside the query's %d", k, i, o.column,
+                      q->num_columns);
+        if (std::find(info.cols.begin(), info.cols.end(), o.column) == info.cols.end()) info.cols.push_back(o.column);
+        depth++;
+        break;
+      case PHIP_EXPR_OP_PUSH_DOUBLE: info.all_long = false;  // fallthrough
+      case PHIP_EXPR_OP_PUSH_LONG: depth++; break;
+      case PHIP_EXPR_OP_DIV: info.has_div = true;  // fallthrough
+      case PHIP_EXPR_OP_ADD:
+      case PHIP_EXPR_OP_SUB:
+      case PHIP_EXPR_OP_MUL:
+        if (depth < 2) return fail(PHIP_ERR_INVALID, "derived column %d: op %d pops an empty stack", k, i);
+        depth--;
+        break;
+      default: return fail(PHIP_ERR_INVALID, "derived column %d: op %d has unknown code %d", k, i, o.op);
+    }
+    if (depth > PHIP_EXPR_MAX_STACK)
+      return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: stack deeper than %d", k, PHIP_EXPR_MAX_STACK);
+  }
+  if (depth != 1) return fail(PHIP_ERR_INVALID, "derived column %d: the program leaves %d values", k, depth);
+  if ((int)info.cols.size() > PHIP_EXPR_MAX_COLUMNS)
+    return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: %d distinct columns, at most %d", k, (int)info.cols.size(),
+                PHIP_EXPR_MAX_COLUMNS);
+  return PHIP_OK;
+}
+
+// Interval arithmetic over one segment's value ranges: the program's result interval when every leaf is an INT / LONG
+// column with a known range or a PUSH_LONG, no DIV occurs and every intermediate's magnitude stays below 2^62 (the
+// `integral` rule of the two-operand forms, generalised); false otherwise.
+bool expr_int_interval(const phip_derived_column &d, const Segment &sg, const std::vector<int> &colidx, long double *lo_out,
+                       long double *hi_out) {
+  const long double lim = (long double)((int64_t)1 << 62);
+  long double lo[PHIP_EXPR_MAX_STACK], hi[PHIP_EXPR_MAX_STACK];
+  int sp = 0;
+  for (int i = 0; i < d.num_ops; i++) {
+    const phip_expr_op &o = d.ops[i];
+    if (o.op == PHIP_EXPR_OP_PUSH_COLUMN) {
+      const ColumnStore &c = sg.cols[colidx[o.column]];
+      if ((c.type != PHIP_TYPE_INT && c.type != PHIP_TYPE_LONG) || !c.has_range) return false;
+      lo[sp] = (long double)c.vmin;
+      hi[sp] = (long double)c.vmax;
+      sp++;
+    } else if (o.op == PHIP_EXPR_OP_PUSH_LONG) {
+      lo[sp] = hi[sp] = (long double)o.long_value;
+      sp++;
+    } else if (o.op == PHIP_EXPR_OP_ADD || o.op == PHIP_EXPR_OP_SUB || o.op == PHIP_EXPR_OP_MUL) {
+      const long double al = lo[sp - 2], ah = hi[sp - 2], bl = lo[sp - 1], bh = hi[sp - 1];
+      sp--;
+      if (o.op == PHIP_EXPR_OP_ADD) {
+        lo[sp - 1] = al + bl;
+        hi[sp - 1] = ah + bh;
+      } else if (o.op == PHIP_EXPR_OP_SUB) {
+        lo[sp - 1] = al - bh;
+        hi[sp - 1] = ah - bl;
+      } else {
+        const long double p[4] = {al * bl, al * bh, ah * bl, ah * bh};
+        lo[sp - 1] = *std::min_element(p, p + 4);
+        hi[sp - 1] = *std::max_element(p, p + 4);
+      }
+    } else {
+      return false;  // PUSH_DOUBLE, DIV
+    }
+    if (std::max(fabsl(lo[sp - 1]), fabsl(hi[sp - 1])) >= lim) return false;
+  }
+  *lo_out = lo[0];
+  *hi_out = hi[0];
+  return true;
+}
+
+uint64_t derived_budget() {
+  const char *e = getenv("PHIP_DERIVED_MAX_BYTES");  // per device; default: the records' budget
+  return e ? (uint64_t)atoll(e) : kRecordBudget;
+}
+
+// Takes a derived column out of its segment's list and clears its column slot (the slot's ColumnStore would otherwise
+// keep a pointer to values that may be freed).
+void erase_derived(Segment &sg, size_t idx) {
+  const int col = sg.base_cols + sg.derived[idx].slot;
+  if (col < (int)sg.cols.size()) sg.cols[col] = ColumnStore();
+  sg.derived.erase(sg.derived.begin() + idx);
+}
+
+// The columns one plan creation has to evaluate: registered with their segments by ensure_derived, evaluated together
+// by build_derived -- one device copy of all the programs, the launches, one synchronisation -- or taken out of the
+// segments again by drop_derived when plan creation fails before that.
+struct DerivedJobs {
+  struct Job {
+    Segment *sg;
+    std::string key;
+    void *out;
+    bool integral;
+  };
+  std::vector<DevExpr> progs;
+  std::vector<Job> jobs;
+};
+void drop_derived(DerivedJobs &dj) {
+  for (const DerivedJobs::Job &j : dj.jobs)
+    for (size_t i = 0; i < j.sg->derived.size(); i++)
+      if (j.sg->derived[i].key == j.key) {
+        erase_derived(*j.sg, i);
+        break;
+      }
+  dj.jobs.clear();
+  dj.progs.clear();
+}
+int32_t build_derived(DerivedJobs &dj, hipStream_t st) {
+  if (dj.jobs.empty()) return PHIP_OK;
+  void *dev_progs = nullptr;
+  hipError_t e = hipMalloc(&dev_progs, dj.progs.size() * sizeof(DevExpr));
+  if (e == hipSuccess) e = hipMemcpyAsync(dev_progs, dj.progs.data(), dj.progs.size() * sizeof(DevExpr), hipMemcpyHostToDevice, st);
+  for (size_t i = 0; i < dj.jobs.size() && e == hipSuccess; i++)
+    e = g_expr_launcher(static_cast<const DevExpr *>(dev_progs) + i, dj.progs[i].num_docs, dj.jobs[i].integral,
+                        dj.jobs[i].out, st);
+  const hipError_t e2 = hipStreamSynchronize(st);  // (the host and device copies of the programs are read until here)
+  if (dev_progs) (void)hipFree(dev_progs);
+  if (e != hipSuccess || e2 != hipSuccess) {
+    drop_derived(dj);
+    return fail(PHIP_ERR_HIP, "derived columns: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  for (const DerivedJobs::Job &j : dj.jobs) j.sg->derived_builds++;
+  dj.jobs.clear();
+  dj.progs.clear();
+  return PHIP_OK;
+}
+
+// The segment's derived column of program d in the given value kind: found by its canonical key (every pushed column
+// resolved to the segment's own column, constants by value) or registered now and queued in `dj` for build_derived
+// (expr.hip), which the caller runs before the plan's first use of it. Returns its slot in sg.cols. Called under the
+// device's mutex. A full segment evicts its least recently used column; past the device's budget the least recently
+// used columns of the query's segments that no plan reads go first.
+int32_t ensure_derived(Segment &sg, const std::vector<Segment *> &segs, const phip_derived_column &d,
+                       const std::vector<int> &colidx, bool integral, long double lo, long double hi, DerivedJobs &dj,
+                       std::shared_ptr<DerivedBuf> *out_buf, int *out_col) {
+  DevExpr de;
+  memset(&de, 0, sizeof(de));
+  std::string key = integral ? "i" : "d";
+  std::vector<int> local;  // the segment's columns, in first-push order
+  char buf[64];
+  for (int i = 0; i < d.num_ops; i++) {
+    const phip_expr_op &o = d.ops[i];
+    DevExprOp &x = de.ops[i];
+    if (o.op == PHIP_EXPR_OP_PUSH_COLUMN) {
+      const int ci = colidx[o.column];
+      auto it = std::find(local.begin(), local.end(), ci);
+      if (it == local.end()) it = local.insert(local.end(), ci);
+      x.op = EXOP_COLUMN;
+      x.col = (int32_t)(it - local.begin());
+      snprintf(buf, sizeof buf, ";c%d", ci);
+    } else if (o.op == PHIP_EXPR_OP_PUSH_LONG || o.op == PHIP_EXPR_OP_PUSH_DOUBLE) {
+      x.op = EXOP_CONST;
+      x.lval = o.long_value;
+      x.dval = o.op == PHIP_EXPR_OP_PUSH_LONG ? (double)o.long_value : o.double_value;
+      uint64_t bits;
+      memcpy(&bits, &x.dval, 8);
+      if (integral) snprintf(buf, sizeof buf, ";l%lld", (long long)x.lval);
+      else snprintf(buf, sizeof buf, ";d%llx", (unsigned long long)bits);
+    } else {
+      x.op = o.op == PHIP_EXPR_OP_ADD ? EXOP_ADD : o.op == PHIP_EXPR_OP_SUB ? EXOP_SUB
+             : o.op == PHIP_EXPR_OP_MUL ? EXOP_MUL : EXOP_DIV;
+      snprintf(buf, sizeof buf, ";%c", "+-*/"[x.op - EXOP_ADD]);
+    }
+    key += buf;
+  }
+  de.num_ops = d.num_ops;
+  de.num_docs = sg.num_docs;
+  const uint64_t now = ++g_derived_clock;
+  for (Segment::Derived &e : sg.derived)
+    if (e.key == key) {
+      e.last_use = now;
+      *out_buf = e.buf;
+      *out_col = sg.base_cols + e.slot;
+      return PHIP_OK;
+    }
+  for (size_t j = 0; j < local.size(); j++) {
+    const ColumnStore &cs = sg.cols[local[j]];
+    DevCol &dc = de.cols[j];
+    dc.words = cs.words;
+    dc.dict = cs.dict;
+    dc.raw = cs.raw;
+    dc.bits = cs.bits;
+    dc.card = cs.card;
+    dc.type = cs.type;
+    dc.has_dict = !no_dict(cs);
+    if (dc.has_dict && (cs.words == nullptr || cs.dict == nullptr))
+      return fail(PHIP_ERR_UNSUPPORTED, "derived column over column %s, which has no forward index to read", cs.name.c_str());
+    if (!dc.has_dict && cs.raw == nullptr)
+      return fail(PHIP_ERR_UNSUPPORTED, "derived column over column %s, which has no values to read", cs.name.c_str());
+    dc.lds_off = -1;
+  }
+  const uint64_t bytes = (uint64_t)std::max<int32_t>(sg.num_docs, 1) * 8 + 16;  // (padded as raw columns are)
+  if (sg.device < 0 || sg.device >= kMaxRecordDevices) return fail(PHIP_ERR_UNSUPPORTED, "derived columns: device %d", sg.device);
+  const uint64_t budget = derived_budget();
+  uint64_t evictable = 0;
+  for (Segment *s2 : segs)
+    for (const Segment::Derived &e : s2->derived)
+      if (e.buf.use_count() == 1) evictable += e.buf->bytes;
+  if (g_derived_bytes[sg.device] + bytes > budget + evictable)  // (nothing is evicted for a column that cannot fit)
+    return fail(PHIP_ERR_UNSUPPORTED, "derived column of %llu bytes: PHIP_DERIVED_MAX_BYTES (%llu) is taken by columns "
+                "that plans still read", (unsigned long long)bytes, (unsigned long long)budget);
+  while (g_derived_bytes[sg.device] + bytes > budget) {
+    Segment *vs = nullptr;
+    size_t vi = 0;
+    for (Segment *s2 : segs)
+      for (size_t j = 0; j < s2->derived.size(); j++)
+        if (s2->derived[j].buf.use_count() == 1 && (!vs || s2->derived[j].last_use < vs->derived[vi].last_use)) {
+          vs = s2;
+          vi = j;
+        }
+    if (!vs)
+      return fail(PHIP_ERR_UNSUPPORTED, "derived column of %llu bytes: PHIP_DERIVED_MAX_BYTES (%llu) is taken by columns "
+                  "that plans still read", (unsigned long long)bytes, (unsigned long long)budget);
+    erase_derived(*vs, vi);  // (frees the values: no plan holds them)
+  }
+  int slot = -1;
+  if ((int)sg.derived.size() >= kMaxDerivedPerSegment) {
+    size_t vi = 0;
+    for (size_t j = 1; j < sg.derived.size(); j++)
+      if (sg.derived[j].last_use < sg.derived[vi].last_use) vi = j;
+    slot = sg.derived[vi].slot;  // (a plan that reads the evicted column keeps its values alive)
+    erase_derived(sg, vi);
+  } else {
+    std::vector<bool> used(kMaxDerivedPerSegment, false);
+    for (const Segment::Derived &e : sg.derived) used[e.slot] = true;
+    for (int j = 0; j < kMaxDerivedPerSegment && slot < 0; j++)
+      if (!used[j]) slot = j;
+  }
+  auto db = std::make_shared<DerivedBuf>();
+  db->device = sg.device;
+  HIP_TRY(hipMalloc(&db->p, bytes));
+  db->bytes = bytes;
+  g_derived_bytes[sg.device] += bytes;
+  if (sg.num_docs > 0) {
+    dj.progs.push_back(de);
+    dj.jobs.push_back({&sg, key, db->p, integral});
+  }
+  ColumnStore cs;
+  cs.name = "derived(" + key + ")";
+  cs.type = integral ? PHIP_TYPE_LONG : PHIP_TYPE_DOUBLE;
+  cs.fwd_kind = PHIP_FWD_RAW_CHUNK;
+  cs.raw = db->p;
+  if (integral) {
+    cs.has_range = true;
+    cs.vmin = (int64_t)lo;
+    cs.vmax = (int64_t)hi;
+  }
+  const int col = sg.base_cols + slot;
+  if (col < (int)sg.cols.size()) sg.cols[col] = std::move(cs);
+  else {
+    // slots fill in order while none is free below: col == cols.size() here (within the reserved capacity)
+    while ((int)sg.cols.size() < col) sg.cols.emplace_back();
+    sg.cols.push_back(std::move(cs));
+  }
+  Segment::Derived nd;
+  nd.key = key;
+  nd.slot = slot;
+  nd.last_use = now;
+  nd.buf = db;
+  sg.derived.push_back(std::move(nd));
+  *out_buf = db;
+  *out_col = col;
+  return PHIP_OK;
+}
+
+}  // namespace
+
 static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t filter_nwords, Plan &P) {
 
   if (!q || q->num_segments <= 0 || q->num_columns < 0 || q->num_columns > kMaxQueryColumns)
@@ -2271,16 +2592,122 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   hipStream_t st = dev->stream;
   P.dev = dev;
 
-  const int nseg = q->num_segments, ncols = q->num_columns, naggs = q->num_aggregations;
+  const int nseg = q->num_segments, nreal = q->num_columns, naggs = q->num_aggregations;
   // resolve columns
-  std::vector<std::vector<int>> colidx(nseg, std::vector<int>(ncols, -1));
+  std::vector<std::vector<int>> colidx(nseg, std::vector<int>(nreal, -1));
   for (int s = 0; s < nseg; s++)
-    for (int c = 0; c < ncols; c++) {
+    for (int c = 0; c < nreal; c++) {
       auto it = segs[s]->by_name.find(q->columns[c]);
       if (it == segs[s]->by_name.end())
         return fail(PHIP_ERR_NOT_FOUND, "segment %s has no column %s", segs[s]->name.c_str(), q->columns[c]);
       colidx[s][c] = it->second;
     }
+
+  // Derived value columns (include/pinot_hip.h phip_expr_op): each (program, value kind) an aggregation reads becomes
+  // one more column of the query -- index nreal + j, a raw LONG / DOUBLE column of every segment, evaluated on first
+  // use (ensure_derived) -- and the aggregation is rewritten to read it. Everything below sees raw columns only; the
+  // programs' own input columns are resolved above and otherwise untouched (not projected, staged or recorded).
+  phip_query_desc qd;
+  std::vector<phip_aggregation> derived_aggs;
+  std::vector<std::vector<int>> derived_inputs;  // per column nreal + j: the query columns its program reads
+  if (q->num_derived < 0 || (q->num_derived > 0 && !q->derived)) return fail(PHIP_ERR_INVALID, "query: bad derived columns");
+  if (q->num_derived > 0) {
+    const int nd = q->num_derived;
+    if (!g_expr_launcher)
+      return fail(PHIP_ERR_UNSUPPORTED, "derived value columns: this library was built without the expression kernel");
+    // a derived index anywhere but column_a of a plain SUM / MIN / MAX / DISTINCTCOUNTHLL is misuse
+    for (int k = 0; k < q->num_group_by && q->group_by_columns; k++)
+      if (q->group_by_columns[k] >= nreal) return fail(PHIP_ERR_INVALID, "group-by column %d is a derived column", k);
+    if (q->filter_offsets && q->filter_nodes)
+      for (int i = q->filter_offsets[0]; i < q->filter_offsets[nprog * nseg]; i++)
+        if (q->filter_nodes[i].op == PHIP_NODE_LEAF && q->filter_nodes[i].column >= nreal)
+          return fail(PHIP_ERR_INVALID, "filter leaf %d reads a derived column", i);
+    for (int k = 0; k < q->num_select && q->select; k++)
+      if (q->select[k].column_a >= nreal || (q->select[k].expr != PHIP_EXPR_COLUMN && q->select[k].column_b >= nreal))
+        return fail(PHIP_ERR_INVALID, "select expression %d reads a derived column", k);
+    std::vector<ExprInfo> info(nd);
+    for (int k = 0; k < nd; k++) {
+      int32_t rc = check_expr_program(q, k, info[k]);
+      if (rc) return rc;
+      for (int c : info[k].cols)
+        for (int s = 0; s < nseg; s++) {
+          const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+          if (cs.type == PHIP_TYPE_STRING)
+            return fail(PHIP_ERR_INVALID, "derived column %d: numeric expression over STRING column %s", k, cs.name.c_str());
+          if (cs.fwd_kind == PHIP_FWD_HLL_REGISTERS)
+            return fail(PHIP_ERR_INVALID, "derived column %d: expression over the HLL register column %s", k, cs.name.c_str());
+        }
+    }
+    derived_aggs.assign(q->aggregations, q->aggregations + (q->aggregations ? naggs : 0));
+    struct Use {
+      int k;
+      bool integral;
+      std::vector<long double> lo, hi;  // per segment (integral)
+    };
+    std::vector<Use> uses;
+    for (int a = 0; a < (int)derived_aggs.size(); a++) {
+      phip_aggregation &ag = derived_aggs[a];
+      if (ag.function == PHIP_AGG_COUNT) continue;
+      if (ag.expr != PHIP_EXPR_COLUMN && ag.column_b >= nreal)
+        return fail(PHIP_ERR_INVALID, "aggregation %d: a derived column as an operand of a two-column expression", a);
+      if (ag.column_a < nreal) continue;
+      const int k = ag.column_a - nreal;
+      if (k >= nd) return fail(PHIP_ERR_INVALID, "aggregation column out of range");
+      if (ag.expr != PHIP_EXPR_COLUMN)
+        return fail(PHIP_ERR_INVALID, "aggregation %d: a derived column as an operand of a two-column expression", a);
+      if (ag.function != PHIP_AGG_SUM && ag.function != PHIP_AGG_MIN && ag.function != PHIP_AGG_MAX &&
+          ag.function != PHIP_AGG_HLL)
+        return fail(PHIP_ERR_INVALID, "aggregation %d: a derived column is the argument of SUM, MIN, MAX or DISTINCTCOUNTHLL only", a);
+      // value kind: exact int64 for a SUM whose program and whole-plan bound allow it (the bound the SUM itself takes
+      // below, sum over segments of max |value| x docs < 2^58); double -- the reference's own computation -- otherwise
+      Use u;
+      u.k = k;
+      u.integral = ag.function == PHIP_AGG_SUM && info[k].all_long && !info[k].has_div;
+      if (u.integral) {
+        long double bound = 0;
+        u.lo.resize(nseg);
+        u.hi.resize(nseg);
+        for (int s = 0; s < nseg && u.integral; s++) {
+          u.integral = expr_int_interval(q->derived[k], *segs[s], colidx[s], &u.lo[s], &u.hi[s]);
+          if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segs[s]->num_docs;
+        }
+        if (bound >= (long double)((int64_t)1 << 58)) u.integral = false;
+      }
+      int j = -1;
+      for (size_t i = 0; i < uses.size(); i++)
+        if (uses[i].k == k && uses[i].integral == u.integral) j = (int)i;
+      if (j < 0) {
+        j = (int)uses.size();
+        uses.push_back(u);
+      }
+      ag.column_a = nreal + j;
+    }
+    if (nreal + (int)uses.size() > kMaxQueryColumns)
+      return fail(PHIP_ERR_UNSUPPORTED, "query: %d columns and %d derived value columns, at most %d in all", nreal,
+                  (int)uses.size(), kMaxQueryColumns);
+    DerivedJobs jobs;
+    for (const Use &u : uses) {
+      derived_inputs.push_back(info[u.k].cols);
+      for (int s = 0; s < nseg; s++) {
+        std::shared_ptr<DerivedBuf> buf;
+        int col = -1;
+        int32_t rc = ensure_derived(*segs[s], segs, q->derived[u.k], colidx[s], u.integral, u.integral ? u.lo[s] : 0,
+                                    u.integral ? u.hi[s] : 0, jobs, &buf, &col);
+        if (rc) {
+          drop_derived(jobs);
+          return rc;
+        }
+        P.derived_bufs.push_back(buf);  // (pinned from here on: a later eviction in this loop cannot free it)
+        colidx[s].push_back(col);
+      }
+    }
+    int32_t rc = build_derived(jobs, st);  // every new column of the plan: one copy of the programs, one synchronisation
+    if (rc) return rc;
+    qd = *q;
+    qd.aggregations = derived_aggs.data();
+    q = &qd;
+  }
+  const int ncols = nreal + (int)derived_inputs.size();
 
   // A group-by whose mixed-radix key space exceeds 2^62 groups by tuple keys (build_tuple_keys): the plan is made for
   // one virtual key column (the first group-by column's slot carries its ids) and execute_plan expands the keys.
@@ -2712,7 +3139,26 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     std::vector<bool> counted = projected;  // (tuple keys: the query's own group-by columns are the projected ones)
     if (P.tuple_keys)
       for (int k = 0; k < (int)P.tuple_dicts.size(); k++) counted[P.tuple_cols[k]] = true;
+    // (a derived column: the reference's projection reads its program's columns -- numEntriesScannedPostFilter)
+    for (int j = 0; j < (int)derived_inputs.size(); j++) {
+      if (!counted[nreal + j]) continue;
+      counted[nreal + j] = false;
+      for (int c : derived_inputs[j]) counted[c] = true;
+    }
     for (bool p : counted) num_projected += p ? 1 : 0;
+  }
+  // ... and per filter program (several programs: each info's own projection): the distinct columns its functions
+  // read, a derived column standing for its program's columns
+  std::vector<int> prog_projected(nprog, 0);
+  for (int p = 0; p < nprog; p++) {
+    std::vector<bool> counted(ncols, false);
+    for (int c = 0; c < ncols; c++) {
+      if (!projected[c] || !((proj_progs[c] >> p) & 1u)) continue;
+      if (c < nreal) counted[c] = true;
+      else
+        for (int i : derived_inputs[c - nreal]) counted[i] = true;
+    }
+    for (bool b : counted) prog_projected[p] += b ? 1 : 0;
   }
 
   // group-by key space
@@ -4127,6 +4573,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   P.m_regs = m_regs;
   P.num_group_by = q->num_group_by;
   P.num_projected = num_projected;
+  P.prog_projected = prog_projected;
   P.num_groups_limit = q->num_groups_limit;
   if (q->trim_size > 0 && q->num_order_terms > 0) {
     if (q->num_order_terms > kMaxOrderKeys || q->num_group_by > kMaxOrderKeys || !q->order_terms)
@@ -4880,9 +5327,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
       for (int p = 0; p < P.nprog; p++) {
         int64_t mp = 0;
         for (int s = 0; s < nseg; s++) mp += has_filter ? (int64_t)segm[p * nseg + s] : P.slot_docs[p * nseg + s];
-        int np = 0;
-        for (const Plan::ProjCol &pc : P.proj) np += (pc.progs >> p) & 1u;
-        st6[2] += mp * np;
+        st6[2] += mp * P.prog_projected[p];
       }
     }
     if (has_filter) {  // a segment matched when any of its programs did
@@ -5727,6 +6172,8 @@ PHIP_API int32_t phip_segment_load(const phip_segment_desc *desc, uint64_t *out_
   for (void *p : temps) (void)hipFree(p);
   if (rc == PHIP_OK && se != hipSuccess) rc = fail(PHIP_ERR_HIP, "segment load: %s", hipGetErrorString(se));
   if (rc != PHIP_OK) return rc;  // the partial segment frees itself
+  seg->base_cols = (int)seg->cols.size();
+  seg->cols.reserve(seg->cols.size() + kMaxDerivedPerSegment);  // (the derived columns' slots: `cols` never moves)
   seg->handle = g_next_handle++;
   *out_handle = seg->handle;
   std::lock_guard<std::mutex> g(g_mu);
@@ -5762,6 +6209,26 @@ PHIP_API int32_t phip_segment_device_bytes(uint64_t handle, uint64_t *out_bytes)
   auto it = g_segments.find(handle);
   if (it == g_segments.end()) return fail(PHIP_ERR_NOT_FOUND, "unknown segment handle");
   if (out_bytes) *out_bytes = it->second->device_bytes;
+  return PHIP_OK;
+}
+
+PHIP_API int32_t phip_segment_derived_info(uint64_t handle, int32_t *out_count, int64_t *out_bytes, int64_t *out_builds) {
+  std::shared_ptr<Segment> seg;
+  Device *dev;
+  {
+    std::lock_guard<std::mutex> g(g_mu);
+    auto it = g_segments.find(handle);
+    if (it == g_segments.end()) return fail(PHIP_ERR_NOT_FOUND, "unknown segment handle");
+    seg = it->second;
+    dev = find_device(seg->device);
+  }
+  if (!dev) return fail(PHIP_ERR_NO_DEVICE, "device %d not initialised", seg->device);
+  std::lock_guard<std::mutex> dl(dev->mu);  // (the derived columns' lock: ensure_derived)
+  int64_t bytes = 0;
+  for (const Segment::Derived &d : seg->derived) bytes += (int64_t)d.buf->bytes;
+  if (out_count) *out_count = (int32_t)seg->derived.size();
+  if (out_bytes) *out_bytes = bytes;
+  if (out_builds) *out_builds = seg->derived_builds;
   return PHIP_OK;
 }
 

@@ -412,8 +412,105 @@ def _strip_cast(e):
     return e
 
 
-def _gpu_expr(e):
-    """Aggregation argument -> (PHIP_EXPR_*, col_a, col_b)."""
+_ARITH = {"plus": _lib.EXPR_OP_ADD, "minus": _lib.EXPR_OP_SUB, "times": _lib.EXPR_OP_MUL, "divide": _lib.EXPR_OP_DIV}
+
+
+class ExprProgram:
+    """A derived value column (include/pinot_hip.h phip_expr_op): an arithmetic aggregation argument compiled to a
+    postfix program, which the library evaluates once per segment into a doc-order column. ``ops``: tuples (op, column
+    name or None, long value, double value). Programs are equal when their ops are, so identical arguments share one
+    derived column and one primitive. ``tree``: the argument with its casts stripped and its literal subtrees folded
+    (the divisors' intervals, _refuse_nan_extrema); ``int_cast_columns``: columns under a cast to INT / LONG, which
+    must be INT / LONG themselves (the reference truncates such a cast's value, the oracle does not)."""
+
+    def __init__(self, ops, tree, int_cast_columns=()):
+        self.ops = tuple(ops)
+        self.tree = tree
+        self.int_cast_columns = tuple(int_cast_columns)
+        self.columns = []
+        for o in self.ops:
+            if o[0] == _lib.EXPR_OP_PUSH_COLUMN and o[1] not in self.columns:
+                self.columns.append(o[1])
+
+    def __eq__(self, other):
+        return isinstance(other, ExprProgram) and self.ops == other.ops
+
+    def __hash__(self):
+        return hash(self.ops)
+
+    def __repr__(self):
+        return f"ExprProgram({self.tree})"
+
+    __str__ = __repr__
+
+
+def _fold_literals(name, a, b):
+    """Literal(a) op Literal(b): in Python ints when both are ints, the op is not a division and the result is an
+    int64 that the double computation reaches too (so both value kinds of the column read one constant); in double, as
+    the reference's LiteralTransformFunction operands are, otherwise."""
+    with np.errstate(all="ignore"):
+        fa, fb = np.float64(a), np.float64(b)
+        f = float({"plus": fa + fb, "minus": fa - fb, "times": fa * fb, "divide": fa / fb}[name])
+    if isinstance(a, int) and isinstance(b, int) and name != "divide":
+        i = {"plus": a + b, "minus": a - b, "times": a * b}[name]
+        if -2 ** 63 <= i < 2 ** 63 and float(i) == f and int(f) == i:
+            return Literal(i)
+    return Literal(f)
+
+
+def _compile_expr(e, ops, int_casts, under_int_cast=False):
+    """Postfix ops of the arithmetic expression ``e`` appended to ``ops``; returns the folded tree."""
+    if isinstance(e, Function) and e.name == "cast":
+        typ = str(e.args[1].value).upper() if len(e.args) > 1 and isinstance(e.args[1], Literal) else ""
+        return _compile_expr(e.args[0], ops, int_casts, under_int_cast or typ in ("INT", "INTEGER", "LONG", "BIGINT"))
+    if isinstance(e, Identifier):
+        if under_int_cast and e.name not in int_casts:
+            int_casts.append(e.name)
+        ops.append((_lib.EXPR_OP_PUSH_COLUMN, e.name, 0, 0.0))
+        return e
+    if isinstance(e, Literal) and isinstance(e.value, (int, float)) and not isinstance(e.value, bool):
+        if isinstance(e.value, int) and -2 ** 63 <= e.value < 2 ** 63:
+            ops.append((_lib.EXPR_OP_PUSH_LONG, None, e.value, float(e.value)))
+        else:
+            if under_int_cast:
+                raise UnsupportedOnGpu(f"cast of the non-integral literal {e} to INT / LONG in an aggregation argument")
+            ops.append((_lib.EXPR_OP_PUSH_DOUBLE, None, 0, float(e.value)))
+        return e
+    if isinstance(e, Function) and e.name in _ARITH and len(e.args) == 2:
+        if under_int_cast and e.name == "divide":
+            raise UnsupportedOnGpu(f"cast of the non-integral expression {e} to INT / LONG: the reference truncates it")
+        mark = len(ops)
+        a = _compile_expr(e.args[0], ops, int_casts, under_int_cast)
+        b = _compile_expr(e.args[1], ops, int_casts, under_int_cast)
+        # (minus(0, x) -- a unary minus -- stays a subtraction: 0 - x is +0.0 where -x is -0.0)
+        if isinstance(a, Literal) and isinstance(b, Literal):
+            del ops[mark:]
+            return _compile_expr(_fold_literals(e.name, a.value, b.value), ops, int_casts, under_int_cast)
+        ops.append((_ARITH[e.name], None, 0, 0.0))
+        return Function(e.name, (a, b))
+    raise UnsupportedOnGpu(f"aggregation argument {e} is outside the GPU expression subset")
+
+
+def _check_program(ops, e):
+    if len(ops) > _lib.EXPR_MAX_OPS:
+        raise UnsupportedOnGpu(f"aggregation argument {e}: {len(ops)} operations, at most {_lib.EXPR_MAX_OPS} on the GPU path")
+    depth = deepest = 0
+    for o in ops:
+        depth += 1 if o[0] <= _lib.EXPR_OP_PUSH_DOUBLE else -1
+        deepest = max(deepest, depth)
+    if deepest > _lib.EXPR_MAX_STACK:
+        raise UnsupportedOnGpu(f"aggregation argument {e}: a value stack of {deepest}, at most {_lib.EXPR_MAX_STACK} on the "
+                               f"GPU path")
+    ncol = len({o[1] for o in ops if o[0] == _lib.EXPR_OP_PUSH_COLUMN})
+    if ncol > _lib.EXPR_MAX_COLUMNS:
+        raise UnsupportedOnGpu(f"aggregation argument {e}: {ncol} columns, at most {_lib.EXPR_MAX_COLUMNS} on the GPU path")
+
+
+def _gpu_expr(e, derived=True):
+    """Aggregation argument -> (PHIP_EXPR_*, col_a, col_b): a column, a two-column plus / minus / times, or -- any
+    other arithmetic over columns and numeric literals -- (PHIP_EXPR_COLUMN, ExprProgram, None), a derived value
+    column (``derived`` False: refused, for the selection's expressions)."""
+    full = e
     e = _strip_cast(e)
     if isinstance(e, Identifier):
         return _lib.EXPR_COLUMN, e.name, None
@@ -422,6 +519,13 @@ def _gpu_expr(e):
         if isinstance(a, Identifier) and isinstance(b, Identifier):
             op = {"times": _lib.EXPR_MUL, "minus": _lib.EXPR_SUB, "plus": _lib.EXPR_ADD}[e.name]
             return op, a.name, b.name
+    if derived and isinstance(e, Function) and e.name in _ARITH and len(e.args) == 2:
+        ops, int_casts = [], []
+        tree = _compile_expr(full, ops, int_casts)
+        if not any(o[0] == _lib.EXPR_OP_PUSH_COLUMN for o in ops):
+            raise UnsupportedOnGpu(f"aggregation argument {e} reads no column")
+        _check_program(ops, e)
+        return _lib.EXPR_COLUMN, ExprProgram(ops, tree, int_casts), None
     raise UnsupportedOnGpu(f"aggregation argument {e} is outside the GPU expression subset")
 
 
@@ -463,7 +567,7 @@ def plan_aggregations(aggs: Sequence[AggregationInfo], programs: Optional[Sequen
             # exact: one bitmap of query-global dictionary ids per column (PHIP_AGG_DISTINCT); the same column twice
             # shares the primitive. Arguments outside a plain column, and other filter programs beside it (FILTER
             # clauses, CASE branches, the null-handling programs), stay with the CPU plan maker.
-            if expr[0] != _lib.EXPR_COLUMN:
+            if expr[0] != _lib.EXPR_COLUMN or isinstance(expr[1], ExprProgram):
                 raise UnsupportedOnGpu("distinctcount of an expression is not on the GPU path")
             if programs is not None:
                 raise UnsupportedOnGpu("distinctcount beside FILTER / CASE / null-handling filter programs")
@@ -472,7 +576,7 @@ def plan_aggregations(aggs: Sequence[AggregationInfo], programs: Optional[Sequen
             # exact: one u32 count per query-global dictionary id of the column (PHIP_AGG_VALUE_COUNTS) -- the multiset
             # of its values, which every percentile and every mode of that column is computed from, so they all share
             # one primitive. The refusals are DISTINCTCOUNT's.
-            if expr[0] != _lib.EXPR_COLUMN:
+            if expr[0] != _lib.EXPR_COLUMN or isinstance(expr[1], ExprProgram):
                 raise UnsupportedOnGpu(f"{f} of an expression is not on the GPU path")
             if programs is not None:
                 raise UnsupportedOnGpu(f"{f} beside FILTER / CASE / null-handling filter programs")
@@ -556,7 +660,17 @@ class GpuCombineOperator:
         cols = []
         for t in self.trees:
             _leaf_columns(t, cols)
+        # derived value columns (ExprProgram arguments): derived[k] is column index len(columns) + k of the descriptor;
+        # the columns a program reads are columns of the query like any other
+        self.derived = []
         for p in self.prims:
+            if isinstance(p[2], ExprProgram):
+                if p[2] not in self.derived:
+                    self.derived.append(p[2])
+                for c in p[2].columns:
+                    if c not in cols:
+                        cols.append(c)
+                continue
             for c in (p[2], p[3]):
                 if c is not None and c not in cols:
                     cols.append(c)
@@ -568,7 +682,70 @@ class GpuCombineOperator:
             for c in cols:
                 if not s.has_column(c):
                     raise KeyError(f"segment {s.name} has no column {c}")
+        self._check_derived(segment_filters is not None)
         self._refuse_nan_extrema()
+
+    def _check_derived(self, star_tree):
+        """What a derived value column's program may read: numeric columns of the segments' own documents."""
+        if not self.derived:
+            return
+        if not self.segments:  # (the value kind and the operands' types are the segments': nothing to decide them by)
+            raise UnsupportedOnGpu("an arithmetic aggregation argument over no segments")
+        if star_tree:
+            raise UnsupportedOnGpu("an arithmetic aggregation argument over a star-tree's documents")
+        for prog in self.derived:
+            for s in self.segments:
+                for c in prog.columns:
+                    m = s.column_metadata(c)
+                    if _STORED[m.data_type] == "STRING":
+                        raise UnsupportedOnGpu(f"arithmetic over the STRING column {c} in {prog}")
+                    if getattr(m, "hll_log2m", 0):
+                        raise UnsupportedOnGpu(f"arithmetic over the HLL register column {c} in {prog}")
+                for c in prog.int_cast_columns:
+                    if _STORED[s.column_metadata(c).data_type] not in ("INT", "LONG"):
+                        raise UnsupportedOnGpu(f"cast of the non-integral column {c} to INT / LONG in {prog}: the "
+                                               f"reference truncates its value")
+
+    @staticmethod
+    def _expr_interval(tree, seg):
+        """(lo, hi) bounding the expression's finite values over one segment (interval arithmetic on the columns'
+        value_interval), or None when unknown (an empty column, a divisor interval over 0, an overflow)."""
+        if isinstance(tree, Literal):
+            return float(tree.value), float(tree.value)
+        if isinstance(tree, Identifier):
+            return seg.value_interval(tree.name)
+        a, b = (GpuCombineOperator._expr_interval(x, seg) for x in tree.args)
+        if a is None or b is None:
+            return None
+        with np.errstate(all="ignore"):
+            if tree.name == "plus":
+                r = (a[0] + b[0], a[1] + b[1])
+            elif tree.name == "minus":
+                r = (a[0] - b[1], a[1] - b[0])
+            else:
+                if tree.name == "divide":
+                    if b[0] <= 0.0 <= b[1]:
+                        return None
+                    b = (1.0 / b[1], 1.0 / b[0])
+                ps = [np.float64(x) * np.float64(y) for x in a for y in b]
+                r = (float(min(ps)), float(max(ps)))
+        return r if np.isfinite(r[0]) and np.isfinite(r[1]) else None
+
+    def _zero_divisor(self, tree):
+        """The first divisor of the expression whose value interval holds 0 in some segment (or is unknown), else
+        None."""
+        if not isinstance(tree, Function):
+            return None
+        for x in tree.args:
+            d = self._zero_divisor(x)
+            if d is not None:
+                return d
+        if tree.name == "divide":
+            for s in self.segments:
+                iv = self._expr_interval(tree.args[1], s)
+                if s.num_docs and (iv is None or iv[0] <= 0.0 <= iv[1]):
+                    return tree.args[1], s
+        return None
 
     def _refuse_nan_extrema(self):
         """MIN / MAX / MINMAXRANGE whose values can be NaN stay with the CPU plan maker. The reference's answer then
@@ -582,8 +759,14 @@ class GpuCombineOperator:
         if not extrema or self._non_scan_fit():
             return
         for p in extrema:
-            arithmetic = p[1] != _lib.EXPR_COLUMN
-            for c in (p[2], p[3]):
+            prog = p[2] if isinstance(p[2], ExprProgram) else None
+            arithmetic = p[1] != _lib.EXPR_COLUMN or prog is not None
+            if prog is not None:  # (a division whose divisor can be 0: 0 / 0 is NaN, x / 0 an infinity)
+                z = self._zero_divisor(prog.tree)
+                if z is not None:
+                    raise UnsupportedOnGpu(f"MIN / MAX / MINMAXRANGE over {prog.tree}: the divisor {z[0]} can be 0 in "
+                                           f"segment {z[1].name}, so its values can be NaN")
+            for c in (prog.columns if prog is not None else (p[2], p[3])):
                 for s in self.segments if c is not None else ():
                     nan, inf = s.real_specials(c)
                     if nan:
@@ -622,6 +805,12 @@ class GpuCombineOperator:
         for i, (f, expr, ca, cb, log2m, prog) in enumerate(self.prims):
             aggs[i].function = f
             aggs[i].expr = expr
+            if isinstance(ca, ExprProgram):  # derived column k: index num_columns + k
+                aggs[i].column_a = len(self.columns) + self.derived.index(ca)
+                aggs[i].column_b = -1
+                aggs[i].log2m = log2m
+                aggs[i].program = prog
+                continue
             aggs[i].column_a = col_index[ca] if ca is not None else -1
             aggs[i].column_b = col_index[cb] if cb is not None else -1
             aggs[i].log2m = log2m
@@ -629,6 +818,21 @@ class GpuCombineOperator:
         keep.append(aggs)
         q.num_aggregations = len(self.prims)
         q.aggregations = aggs
+        if self.derived:
+            dcols = (_lib.DerivedColumn * len(self.derived))()
+            for k, dp in enumerate(self.derived):
+                ops = (_lib.ExprOp * len(dp.ops))()
+                for j, (op, c, lv, dv) in enumerate(dp.ops):
+                    ops[j].op = op
+                    ops[j].column = col_index[c] if c is not None else -1
+                    ops[j].long_value = lv
+                    ops[j].double_value = dv
+                keep.append(ops)
+                dcols[k].ops = ops
+                dcols[k].num_ops = len(dp.ops)
+            keep.append(dcols)
+            q.num_derived = len(self.derived)
+            q.derived = dcols
         gb = (ctypes.c_int32 * max(len(self.query.group_by), 1))(*[col_index[e.name] for e in self.query.group_by])
         keep.append(gb)
         q.num_group_by = len(self.query.group_by)
@@ -1174,7 +1378,7 @@ class GpuSelectionOperator(GpuCombineOperator):
             if isinstance(e2, Identifier):
                 self.sel.append((_lib.EXPR_COLUMN, e2.name, None))
             else:
-                self.sel.append(_gpu_expr(e2))
+                self.sel.append(_gpu_expr(e2, derived=False))
         if len(self.sel) > 16:
             raise UnsupportedOnGpu("selection of more than 16 expressions")
         super().__init__(query, segments, num_groups_limit)

@@ -25,6 +25,7 @@ class GpuSegment:
         self._sorted = {}
         self._inv_offsets = {}
         self._specials = {}  # column -> (holds NaN, holds an infinity): real_specials
+        self._intervals = {}  # column -> (min, max) or None: value_interval
         cols = list(segment.columns.values())
         descs = (_lib.ColumnDesc * max(len(cols), 1))()
         keep = []
@@ -115,6 +116,28 @@ class GpuSegment:
                 flags = (nan, bool(np.isinf(ends).any()))
             self._specials[column] = flags
         return flags
+
+    def value_interval(self, column):
+        """(min, max) of a numeric column's values as floats, NaN left out -- the dictionary's ends, or one read of a
+        raw column's chunks, kept; None for a column without docs or values. For a divisor's interval
+        (plan._refuse_nan_extrema)."""
+        if column not in self._intervals:
+            m = self.column_metadata(column)
+            if m.has_dictionary:
+                v = np.asarray(self.dictionary(column).values)
+            else:
+                v = read_chunk_forward(self.segment.columns[column].forward, m.data_type, self.num_docs)
+            v = np.asarray(v, dtype=np.float64)
+            v = v[~np.isnan(v)]
+            self._intervals[column] = (float(v.min()), float(v.max())) if len(v) else None
+        return self._intervals[column]
+
+    def derived_info(self):
+        """(count, bytes, builds) of the segment's derived value columns (phip_segment_derived_info): how many it holds,
+        their HBM bytes, and the materialise launches since load."""
+        n, b, k = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.load().phip_segment_derived_info(self.handle, ctypes.byref(n), ctypes.byref(b), ctypes.byref(k)))
+        return n.value, b.value, k.value
 
     def inverted_bytes(self, column, dict_ids) -> int:
         """Bytes of the inverted-index bitmaps of `dict_ids` (the bytes an inverted leaf reads)."""
