@@ -622,7 +622,9 @@ PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *
 #define PHIP_SHAPE_DISTINCT_BLOCKS 6 /* upper bound of the distinct pass's workgroups (4 waves each) */
 #define PHIP_SHAPE_SELECT_BLOCKS 7  /* upper bound of the selection passes' workgroups (4 waves each) */
 #define PHIP_SHAPE_FUSED_LEAN 8     /* 1: the filter launch was the lean fused instantiation (bit-sliced + deferred) */
-#define PHIP_LAUNCH_SHAPE_VALUES 9
+#define PHIP_SHAPE_HOST_FINAL 9     /* 1: the execution ran in record mode (tagged per-block records reduced on the host, no
+                                     * finalize launch; PHIP_HOST_FINAL=0 at plan creation keeps the launch) */
+#define PHIP_LAUNCH_SHAPE_VALUES 10
 PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values);
 
 #endif /* PINOT_HIP_H_ */

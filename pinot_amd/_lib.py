@@ -57,7 +57,7 @@ EXCHANGE_HASH = 4
 
 # phip_plan_launch_shape values, in order (include/pinot_hip.h PHIP_SHAPE_*)
 LAUNCH_SHAPE_FIELDS = ("total_work", "filter_blocks", "agg_blocks", "agg_waves", "nbuf", "num_work_segments",
-                       "distinct_blocks", "select_blocks", "fused_lean")
+                       "distinct_blocks", "select_blocks", "fused_lean", "host_final")
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pinot_hip.h"
+#include "acc_ops.h"
 #include "device.h"
 
 namespace phip {
@@ -120,18 +121,7 @@ __device__ __forceinline__ double wave_reduce_f64(double v, int kind) {
   return v;
 }
 
-__device__ __forceinline__ uint64_t acc_init(int kind) {
-  if (kind == ACC_MIN_F64) return as_u64(__builtin_huge_val());
-  if (kind == ACC_MAX_F64) return as_u64(-__builtin_huge_val());
-  return 0;  // counts, int sums, f64 +0.0
-}
-
-__device__ __forceinline__ uint64_t acc_combine(int kind, uint64_t a, uint64_t b) {
-  if (kind == ACC_SUM_F64) return as_u64(as_f64(a) + as_f64(b));
-  if (kind == ACC_MIN_F64) return as_u64(fmin(as_f64(a), as_f64(b)));
-  if (kind == ACC_MAX_F64) return as_u64(fmax(as_f64(a), as_f64(b)));
-  return a + b;
-}
+// acc_init / acc_combine: acc_ops.h (shared with the host's reduction of per-block records)
 
 // s_waitcnt vmcnt(n) for a wave-uniform n (vmcnt takes an immediate; n >= 63 needs no wait: at most
 // 63 vector-memory operations can be outstanding, so an op with 63 younger ones has completed).

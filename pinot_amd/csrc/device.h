@@ -3,6 +3,13 @@
 #pragma once
 #include <stdint.h>
 
+// functions shared by host code and kernels (acc_ops.h, tile_range.h, host_final.h); plain C++ outside hipcc
+#if defined(__HIPCC__)
+#define PHIP_HD __host__ __device__
+#else
+#define PHIP_HD
+#endif
+
 namespace phip {
 
 constexpr int kMaxQueryColumns = 16;  // distinct columns one query may reference
@@ -35,6 +42,10 @@ constexpr int kMaxHllRegs = 1 << 12;  // log2m <= 12 on the GPU path
 constexpr int kFilterBlock = 256;
 constexpr int kFilterWaves = kFilterBlock / kWave;
 constexpr int kMaxRing = 8;           // LDS-DMA ring slots per wave
+// the filter kernel's static LDS at most (filter_kernel.h: block partials 64 B, fused aggregation partials 32 B per
+// accumulator, the record mode's per-wave rows of segment counts 224 B, 16 B of alignment: 432 B with four
+// accumulators); the host sizes the LDS-DMA ring around it
+constexpr int kFilterStaticLds = 448;
 constexpr int kFusedRingTile = 512;   // fused aggregation, per-tile mode: u16 tile-relative doc ids per wave
 #ifndef PHIP_FUSED_RING_DEFER
 #define PHIP_FUSED_RING_DEFER 512  // (A/B builds override it)
@@ -314,7 +325,7 @@ struct DevFilter {
   int32_t mask_nt;          // tile masks stored non-temporally (PHIP_MASK_NT measurement switch)
   uint32_t *mask_out;    // optional: [total_work][64] lane-major tile masks
   uint64_t *partials;    // [num_blocks][2]: matched docs, entries scanned in filter
-  uint64_t *seg_matched; // [num query segments]
+  uint64_t *seg_matched; // [num query segments]; null in record mode (rec below)
   // fused aggregation (conjunctive programs, no group-by / HLL): the filter kernel projects and aggregates
   // each tile's matched docs itself, reading staged columns from the tile's ring slot (DevCol.lds_off)
   const struct DevAggQuery *agg;  // device copy of the aggregation descriptor, null = not fused
@@ -322,6 +333,12 @@ struct DevFilter {
   int32_t fring_bytes;            // per-wave matched-doc ring (fused): 4 * kFusedRingDefer when a segment defers,
   int32_t pad_f;                  // else 2 * kFusedRingTile
   const DevFinal *fin;            // non-null: this launch is the plan's last; its last workgroup finalizes
+  // record mode (host_final.h): non-null = every workgroup ends by storing one tagged record of its partials and its
+  // segment entries' matched counts into mapped host memory, and stores no device partial and no seg_matched atomic
+  uint64_t *rec;             // [num_blocks] records of rec_stride bytes
+  const int32_t *rec_first;  // [num_blocks] first work-list entry of the block's tile range (xcd_walk 0 or 2)
+  int32_t rec_stride;        // 64 or 128
+  uint32_t rec_tag;          // this execution's 16-bit tag (by value: it changes per launch without a copy)
 };
 
 struct DevAgg {

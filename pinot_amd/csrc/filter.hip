@@ -140,6 +140,9 @@ hipError_t launch_filter(const DevFilter &q, FilterVariant variant, int naggs, i
   return hipErrorInvalidValue;
 }
 
+// filter_kernel stores the record mode's records (filter_kernel.h record_store): tell the runtime (launch.h)
+static const bool g_records_registered = (register_filter_records(true), true);
+
 hipError_t launch_masks_to_words(const uint32_t *masks, int32_t tile0, int32_t ntiles, uint64_t *words, int64_t nwords,
                                  hipStream_t s) {
   if (ntiles <= 0) return hipSuccess;

@@ -24,6 +24,7 @@
 #include <hip/hip_ext.h>
 
 #include "agg_kernel.h"  // (the fused group-by flushes through agg_kernel.h's group_ring_batch)
+#include "host_final.h"  // (the record mode's encoding; tile_range.h: the waves' tile ranges)
 
 namespace phip {
 
@@ -1372,6 +1373,36 @@ __device__ __forceinline__ void cursor_issue(StageCursor<kS> &c, uint32_t lbase,
   }
 }
 
+// Record mode (host_final.h): the workgroup's record, after the epilogue's barrier. Lane i of the first wave stores
+// word i -- ONE wave instruction of relaxed system-scope 8-byte stores over 64 or 128 contiguous bytes of mapped host
+// memory. part: [wave][2] matched docs / entries scanned; apart: [wave][NA] the waves' aggregation partials, combined
+// in wave order like the device partial was; segrow: [wave][kRecSegSlots] the waves' per-entry matched counts. Words
+// past the block's own (it touches fewer entries) carry zeros: the host does not read them.
+template <int NA>
+__device__ __forceinline__ void record_store(const DevFilter &q, const uint64_t *part, const uint64_t *apart,
+                                             const uint32_t *segrow) {
+  const int i = (int)threadIdx.x;
+  if (i >= (q.rec_stride >> 3)) return;
+  int na = 0;
+  if constexpr (NA > 0) na = ((cquery_t *)q.agg)->num_aggs;
+  uint64_t v = 0;
+  if (i < 2) {
+    for (int w = 0; w < kFilterWaves; w++) v += part[w * 2 + i];
+  } else if (i < 2 + 2 * na) {
+    if constexpr (NA > 0) {
+      const int a = (i - 2) >> 1, kind = ((cquery_t *)q.agg)->aggs[a].acc;
+      v = apart[a];
+      for (int w = 1; w < kFilterWaves; w++) v = acc_combine(kind, v, apart[w * NA + a]);
+      v = (i & 1) ? (v >> 48) : v;  // (the low 48 bits, then the high 16)
+    }
+  } else {
+    const int e = q.rec_first[blockIdx.x] + (i - 2 - 2 * na);
+    for (int w = 0; w < kFilterWaves; w++) v += segrow[w * kRecSegSlots + e % kRecSegSlots];
+  }
+  __hip_atomic_store(q.rec + (((size_t)blockIdx.x * (uint32_t)q.rec_stride) >> 3) + i, rec_word(q.rec_tag, v),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 #ifndef PHIP_FUSED_WAVES
 #define PHIP_FUSED_WAVES 5  // waves per SIMD the fused launches are compiled for: the LDS admits 5 workgroups (20 waves)
                             // per CU, and 6 left 68 B of spills per lane (sorted Q1.1 -5 %, profiles/r05j_ablib_waves.log)
@@ -1399,22 +1430,14 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
     begin = (int)((int64_t)q.total_work * x / 8) + (int)(blockIdx.x >> 3) * kFilterWaves + wave;
     end = (int)((int64_t)q.total_work * (x + 1) / 8);
     step = gx * kFilterWaves;
-  } else if (q.xcd_walk == 2) {
-    // XCD ranges, each cut into contiguous per-wave ranges: a wave streams contiguous tiles (its ring
-    // prefetch stays sequential) and an XCD's waves stay inside 1/8 of the work list, so the dictionaries a
-    // fused aggregation gathers from belong to the few segments of that range (they stay in the XCD's L2)
-    const int x = blockIdx.x & 7, gx = gridDim.x >> 3;
-    const int64_t xs = (int64_t)q.total_work * x / 8, xe = (int64_t)q.total_work * (x + 1) / 8;
-    const int64_t nw = (int64_t)gx * kFilterWaves, w = (int64_t)(blockIdx.x >> 3) * kFilterWaves + wave;
-    begin = (int)(xs + (xe - xs) * w / nw);
-    end = (int)(xs + (xe - xs) * (w + 1) / nw);
-    step = 1;
   } else {
-    // contiguous range per wave
-    const int64_t waves_total = (int64_t)gridDim.x * kFilterWaves;
-    const int64_t gw = (int64_t)blockIdx.x * kFilterWaves + wave;
-    begin = (int)((int64_t)q.total_work * gw / waves_total);
-    end = (int)((int64_t)q.total_work * (gw + 1) / waves_total);
+    // xcd_walk == 2: XCD ranges, each cut into contiguous per-wave ranges: a wave streams contiguous tiles (its ring
+    // prefetch stays sequential) and an XCD's waves stay inside 1/8 of the work list, so the dictionaries a
+    // fused aggregation gathers from belong to the few segments of that range (they stay in the XCD's L2);
+    // xcd_walk == 0: a contiguous range per wave (tile_range.h: the host's record table computes the same ranges)
+    const TileRange r = wave_tile_range(q.xcd_walk, q.total_work, (int)gridDim.x, (int)blockIdx.x, wave, kFilterWaves);
+    begin = r.begin;
+    end = r.end;
     step = 1;
   }
   const int nbuf = q.nbuf;
@@ -1455,6 +1478,18 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
     }
     for (int i = threadIdx.x; i < aq.hll_words; i += kFilterBlock) ghll[i] = 0;
     __syncthreads();
+  }
+  // record mode (q.rec): the matched count of every work-list entry the wave leaves goes to the wave's own row, slot
+  // entry % kRecSegSlots (a block's range touches at most kRecSegSlots consecutive entries, and a wave meets an entry
+  // once), instead of an atomic on q.seg_matched; the epilogue sums the rows. Each wave clears its own row: no barrier.
+  // Inside the tile loop the mode is read off q.seg_matched (null in record mode), the pointer the other branch needs
+  // anyway: a flag of its own stayed live across the loop and cost the conjunctive and the general fused unit 20 B of
+  // scratch per lane.
+  __shared__ uint32_t segrow[kFilterWaves][NA >= 0 ? kRecSegSlots : 1];
+  if constexpr (NA >= 0) {
+    // (every lane stores, the lanes past the row onto its last slot: under `lane < kRecSegSlots` the conjunctive unit
+    // spilled SGPRs past its 80 VGPRs into 20 B of scratch per lane)
+    segrow[wave][min(lane, kRecSegSlots - 1)] = 0;
   }
   uint64_t acc[NAX];
   SmallDict sda[NAX], sdb[NAX];
@@ -1510,8 +1545,11 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
         const uint64_t m = wave_reduce_u64_add(lane_matched);
         lane_matched = 0;
         matched_total += m;
-        if (m && lane == 0)  // m is wave-uniform: one atomic wave-instruction
+        if (NA >= 0 && q.seg_matched == nullptr) {
+          if (lane == 0) segrow[wave][si % kRecSegSlots] = (uint32_t)m;  // (a segment's docs fit 31 bits)
+        } else if (m && lane == 0) {  // m is wave-uniform: one atomic wave-instruction
           atomicAdd((unsigned long long *)&q.seg_matched[segs[si].seg_index], (unsigned long long)m);
+        }
       }
       si = si < 0 ? 0 : si;
       while (si + 1 < q.num_segs && segs[si + 1].work_begin <= t) si++;
@@ -1587,8 +1625,13 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
   if (si >= 0) {
     const uint64_t m = wave_reduce_u64_add(lane_matched);
     matched_total += m;
-    if (lane == 0 && m) atomicAdd((unsigned long long *)&q.seg_matched[segs[si].seg_index], (unsigned long long)m);
+    if (NA >= 0 && q.seg_matched == nullptr) {
+      if (lane == 0) segrow[wave][si % kRecSegSlots] = (uint32_t)m;
+    } else if (lane == 0 && m) {
+      atomicAdd((unsigned long long *)&q.seg_matched[segs[si].seg_index], (unsigned long long)m);
+    }
   }
+  const bool rec_mode = NA >= 0 && q.rec != nullptr;
   // per-block partials: matched docs, entries scanned in filter (fixed-order reduction on the host side)
   __shared__ uint64_t part[kFilterWaves][2];
   if (lane == 0) {
@@ -1596,7 +1639,7 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
     part[wave][1] = scanned;
   }
   __syncthreads();
-  if (threadIdx.x < 2) {
+  if (!rec_mode && threadIdx.x < 2) {
     uint64_t v = 0;
     for (int w = 0; w < kFilterWaves; w++) v += part[w][threadIdx.x];
     coherent_store(q.partials + (size_t)blockIdx.x * 2 + threadIdx.x, v);  // (read by the finalizing workgroup)
@@ -1604,6 +1647,7 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
   if constexpr (NA > 0) {  // fused aggregation: per-block partials, reduced in a fixed order by finalize
     cquery_t &aq = *(cquery_t *)q.agg;
     __shared__ uint64_t apart[kFilterWaves][NA];
+    static_assert(sizeof(part) + sizeof(apart) + sizeof(segrow) <= kFilterStaticLds, "runtime.cpp sizes the ring by it");
 #pragma unroll
     for (int a = 0; a < NA; a++) {
       if (a >= aq.num_aggs) break;
@@ -1614,7 +1658,7 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
       if (lane == 0) apart[wave][a] = v;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (!rec_mode && threadIdx.x == 0) {
 #pragma unroll
       for (int a = 0; a < NA; a++) {
         if (a >= aq.num_aggs) break;
@@ -1624,6 +1668,10 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
         coherent_store(q.agg_partials + (size_t)blockIdx.x * aq.num_aggs + a, v);
       }
     }
+    if (rec_mode) record_store<NA>(q, &part[0][0], &apart[0][0], &segrow[0][0]);
+  }
+  if constexpr (NA == 0) {
+    if (rec_mode) record_store<0>(q, &part[0][0], nullptr, &segrow[0][0]);
   }
   if constexpr (NA == kFusedGroupByLds) {  // the workgroup's table -> its slab (slab_reduce_kernel folds them in order)
     cquery_t &aq = *(cquery_t *)q.agg;
@@ -1633,7 +1681,7 @@ __global__ __launch_bounds__(kFilterBlock, kConjOnly ? (NA != 0 ? PHIP_FUSED_WAV
     glb_u32 *hs = (glb_u32 *)aq.gb_hll + (size_t)blockIdx.x * aq.hll_words;
     for (int i = threadIdx.x; i < aq.hll_words; i += kFilterBlock) hs[i] = ghll[i];
   }
-  if (q.fin != nullptr) finalize_tail(q.fin);
+  if (!rec_mode && q.fin != nullptr) finalize_tail(q.fin);
 }
 
 

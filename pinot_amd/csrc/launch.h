@@ -33,6 +33,10 @@ hipError_t launch_filter(const DevFilter &q, FilterVariant variant, int naggs, i
                          hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t launch_masks_to_words(const uint32_t *masks, int32_t tile0, int32_t ntiles, uint64_t *words, int64_t nwords,
                                  hipStream_t s);
+// The record mode of aggregation-only plans (host_final.h) rides in DevFilter (rec, rec_first, rec_stride, rec_tag): no
+// launcher signature knows of it. The host simulation's stand-in launch_filter stores no records, so the runtime takes
+// the mode only after filter.hip has said, from a static initialiser, that its kernels do (like ExprLauncher below).
+void register_filter_records(bool on);  // defined in runtime.cpp
 
 // ---- aggregate.hip -----------------------------------------------------------------------------------------------
 hipError_t launch_agg(const DevAggQuery &q, const DevAggQuery *dq, int nblocks, size_t lds, hipStream_t s,

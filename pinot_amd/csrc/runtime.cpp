@@ -28,6 +28,7 @@
 
 #include "../../include/pinot_hip.h"
 #include "device.h"
+#include "host_final.h"
 #include "launch.h"
 #include "node.h"
 
@@ -1927,6 +1928,7 @@ struct Plan {
       if (e) (void)hipEventDestroy(e);
     for (void *p : allocs) (void)hipFree(p);
     if (pinned) (void)hipHostFree(pinned);
+    if (rec_area) (void)hipHostFree(rec_area);
     if (pstage) (void)hipHostFree(pstage);
   }
   // configuration
@@ -2061,6 +2063,18 @@ struct Plan {
   // execution waits for (0: wait for the stream).
   uint32_t *done_ticket = nullptr;
   uint64_t done_counter = 0, done_seq = 0;
+  // Record mode (host_final.h; PHIP_HOST_FINAL=0 keeps the finalize launch): under the conditions of the poll above the
+  // filter kernel's workgroups store tagged records of their partials into `rec_area` (mapped, coherent host memory)
+  // and the host reduces them -- no finalize_all launch. rec_ok: the plan can run it (decided at preparation: a
+  // filter-only or fused aggregation plan whose every block's record fits 128 B); rec_exec: this execution does.
+  bool rec_ok = false, rec_exec = false;
+  uint64_t *rec_area = nullptr, *rec_area_dev = nullptr;
+  int32_t *rec_first_dev = nullptr;
+  int rec_na = 0, rec_stride = 64;
+  uint32_t rec_tag = 0;  // the last execution's tag (16 bits, never 0)
+  RecBlocks rec_blocks;
+  std::vector<int32_t> rec_entry_slot, rec_kinds;
+  std::vector<uint64_t> rec_scratch;  // [filter_blocks] words of the host's reduction
   // PHIP_KERNEL_TIMING=0 (read per execution; aggregation-only plans): no timing markers around the kernels -- two
   // barrier packets the command processor waits on per query -- and kernel times reported as 0
   bool timed = true;
@@ -2273,6 +2287,10 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
 // derived value columns (include/pinot_hip.h phip_expr_op; expr.hip)
 // ================================================================================================
 void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
+// the filter kernels of this library store records (filter.hip registers it; false in a build without the kernel units,
+// whose stand-in launch_filter knows nothing of records)
+static bool g_filter_records = false;
+void phip::register_filter_records(bool on) { g_filter_records = on; }
 
 namespace {
 
@@ -4232,9 +4250,10 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (!env && total_work >= 4 * waves_at && !fused_any)
       while (want > 2 && total_work < kMinTilesPerWave * (int64_t)grid_cus * want * kFilterWaves) want--;
     const int64_t fring = (fused_any ? (int64_t)kFilterWaves * fring_bytes : 0) + gb_lds_bytes;  // fused doc rings (+ table)
+    const int64_t static_lds = fused_gb ? 256 : kFilterStaticLds;  // (the fused group-by holds no record rows)
     for (int bpc = want; bpc >= 1 && nbuf < 2; bpc--) {
-      // a workgroup's share of the CU's 160 KiB, less 256 B for the kernel's static LDS (block partials)
-      const int64_t nb = std::min<int64_t>(kMaxRing, ((160 * 1024) / bpc - 256 - fring) / ((int64_t)kFilterWaves * stage_stride));
+      // a workgroup's share of the CU's 160 KiB, less the kernel's static LDS (block partials, the record mode's rows)
+      const int64_t nb = std::min<int64_t>(kMaxRing, ((160 * 1024) / bpc - static_lds - fring) / ((int64_t)kFilterWaves * stage_stride));
       if (nb >= 2) {
         nbuf = (int)nb;
         fbpc = bpc;
@@ -4248,7 +4267,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     const char *fs = getenv("PHIP_FUSED_SMALL");
     if (!env && fused_any && !(fs && atoi(fs) == 0) &&
         total_work <= (int64_t)dev->num_cus * kFilterWaves * 8 && fbpc > 1) {
-      const int64_t nb = std::min<int64_t>(kMaxRing, ((160 * 1024) - 256 - fring) / ((int64_t)kFilterWaves * stage_stride));
+      const int64_t nb = std::min<int64_t>(kMaxRing, ((160 * 1024) - static_lds - fring) / ((int64_t)kFilterWaves * stage_stride));
       if (nb >= 2) {
         nbuf = (int)nb;
         fbpc = 1;
@@ -4769,6 +4788,46 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     HIP_TRY(hipStreamSynchronize(st));
     P.fold_final = true;
   }
+  // Record mode (host_final.h): a filter-only plan (COUNT) or a fused aggregation, contiguous per-wave ranges, every
+  // block's record within 128 B and every count within its 48-bit field. A plan that fails a condition keeps the
+  // finalize launch.
+  {
+    const char *hf = getenv("PHIP_HOST_FINAL");
+    const bool shape_ok = !group_by && !P.select && !want_bitmap && total_work > 0 && has_filter && nhll == 0 &&
+                          P.ndist == 0 && (fused_naggs > 0 ? P.fused_agg() && naggs <= 4 : !need_agg) &&
+                          (xcd_walk == 0 || xcd_walk == 2) && !P.fold_final && P.done_ticket != nullptr;
+    if (g_filter_records && shape_ok && !(hf && atoi(hf) == 0) && (double)P.total_docs * 64.0 < 281474976710656.0) {
+      std::vector<int32_t> entry_begin(dsegs.size());
+      P.rec_entry_slot.resize(dsegs.size());
+      for (size_t i = 0; i < dsegs.size(); i++) {
+        entry_begin[i] = dsegs[i].work_begin;
+        P.rec_entry_slot[i] = dsegs[i].seg_index;
+      }
+      P.rec_na = fused_naggs > 0 ? naggs : 0;
+      P.rec_blocks = rec_block_table(xcd_walk, (int)total_work, filter_blocks, kFilterWaves, entry_begin);
+      if (rec_num_words(P.rec_na, P.rec_blocks.max_k) <= kRecMaxWords) {
+        P.rec_stride = rec_num_words(P.rec_na, P.rec_blocks.max_k) <= 8 ? 64 : 128;
+        P.rec_kinds.resize(std::max(P.rec_na, 1));
+        P.rec_scratch.resize(filter_blocks);
+        for (int a = 0; a < P.rec_na; a++) P.rec_kinds[a] = dq.aggs[a].acc;
+        void *h = nullptr, *dp = nullptr, *fd = nullptr;
+        const size_t rbytes = (size_t)filter_blocks * P.rec_stride;
+        // coherent on purpose: the host reads the words while the kernel still runs
+        HIP_TRY(hipHostMalloc(&h, rbytes, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(h, 0, rbytes);
+        P.rec_area = (uint64_t *)h;
+        HIP_TRY(hipHostGetDevicePointer(&dp, h, 0));
+        P.rec_area_dev = (uint64_t *)dp;
+        rc = P.alloc((size_t)filter_blocks * 4, &fd);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(fd, P.rec_blocks.first.data(), (size_t)filter_blocks * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        P.rec_first_dev = (int32_t *)fd;
+        if (const char *t0 = getenv("PHIP_HOST_FINAL_TAG0")) P.rec_tag = (uint32_t)atoi(t0) & 0xffffu;  // (test hook)
+        P.rec_ok = true;
+      }
+    }
+  }
   return PHIP_OK;
 }
 
@@ -4848,6 +4907,24 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   const bool ext_events = P.timed && total_work > 0 && nkern == 1 && !P.split_event && xe && atoi(xe) != 0;
   hipEvent_t e0 = ext_events ? P.ev[1] : nullptr, e1 = ext_events ? P.ev[2] : nullptr;
   if (!ext_events && P.timed) HIP_TRY(hipEventRecord(P.ev[1], st));
+  // record mode, under exactly the poll's conditions below (and never inside a captured graph: the tag is a kernel
+  // argument by value)
+  const char *pd = getenv("PHIP_POLL_DONE");  // measurement override: "0" waits for the stream
+  P.rec_exec = P.rec_ok && total_work > 0 && !P.fold_final && P.done_ticket != nullptr && !(pd && atoi(pd) == 0) &&
+               !P.total_events && !P.timed && getenv("PHIP_GRAPH") == nullptr;
+  if (P.rec_exec) {
+    P.rec_tag = rec_next_tag(P.rec_tag);
+    // (a zero-filled word must never read as this execution's: the counter skips 0)
+    if (P.rec_tag == 0 || P.rec_tag > 0xffffu) return fail(PHIP_ERR_HIP, "record mode: execution tag %u", P.rec_tag);
+    fq.rec = P.rec_area_dev;
+    fq.rec_first = P.rec_first_dev;
+    fq.rec_stride = P.rec_stride;
+    fq.rec_tag = P.rec_tag;
+    fq.seg_matched = nullptr;  // (how the kernel's tile loop knows the mode)
+  } else {
+    fq.rec = nullptr;
+    fq.seg_matched = (uint64_t *)seg_matched;
+  }
   if (has_filter && total_work > 0)
     HIP_TRY(launch_filter(fq, P.variant, P.fused_naggs, filter_blocks, filter_lds, st, e0, e1));
   // (a plan of one kernel -- fused, or a filter or aggregation alone -- needs no split event)
@@ -4884,9 +4961,8 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
                                   filter_nwords, st));
   // every result lands in the plan's pinned buffer, written by the device: finals[64] | seg_matched[nmatch] | HLL
   P.done_seq = 0;
-  if (total_work > 0 && !P.fold_final) {
+  if (total_work > 0 && !P.fold_final && !P.rec_exec) {
     const bool aggs_here = need_agg && !group_by && naggs > 0;
-    const char *pd = getenv("PHIP_POLL_DONE");  // measurement override: "0" waits for the stream
     // (only without timing markers: an event's elapsed time is readable once the runtime has seen its command
     // complete, which a poll that returns early does not wait for -- "device not ready" under concurrent lanes)
     const bool poll = P.done_ticket != nullptr && !(pd && atoi(pd) == 0) && !P.total_events && !P.timed;
@@ -5242,7 +5318,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   // measurement only (PHIP_HOST_TRACE=1): host microseconds per phase of this call, one stderr line per execution
   static const bool host_trace = getenv("PHIP_HOST_TRACE") != nullptr;
   using hclock = std::chrono::steady_clock;
-  hclock::time_point ht[5];
+  hclock::time_point ht[5], ht_reduce;  // (ht_reduce: record mode, the last record accepted -- the reduction follows)
   if (host_trace) ht[0] = hclock::now();
   HIP_TRY(hipSetDevice(dev->ordinal));
   LaneGuard lg{dev};
@@ -5276,14 +5352,16 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (mode != EXEC_FINISH) {
     const int32_t sh[PHIP_LAUNCH_SHAPE_VALUES] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves,
                                                   P.fq.nbuf, (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks,
-                                                  P.variant == FV_FUSED_LEAN ? 1 : 0};
+                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0};
     memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {
+    P.rec_exec = false;
     HIP_TRY(hipGraphLaunch(P.graph_exec, st));
   } else if (mode != EXEC_FINISH) {
     int32_t rc = enqueue_plan(P, st);
     if (rc) return rc;
+    P.shape[PHIP_SHAPE_HOST_FINAL] = P.rec_exec ? 1 : 0;
   }
   if (host_trace) ht[2] = hclock::now();
   if (mode != EXEC_FINISH) {
@@ -5628,6 +5706,40 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
       }
       impl->dicts[k] = rd;
     }
+  } else if (P.rec_exec && mode == EXEC_FULL) {
+    // record mode: accept every block's record (all its expected words carry this execution's tag), then reduce them
+    // in finalize_all's fixed order into the result area the assembly below reads. A record missing after the bound
+    // is waited for on the stream (which also reports a failed launch); one missing after that is an internal error.
+    RecPlan rp;
+    rp.nblocks = P.filter_blocks;
+    rp.na = P.rec_na;
+    rp.stride_words = P.rec_stride / 8;
+    rp.kinds = P.rec_kinds.data();
+    rp.first = P.rec_blocks.first.data();
+    rp.k = P.rec_blocks.k.data();
+    rp.entry_slot = P.rec_entry_slot.data();
+    const volatile uint64_t *area = P.rec_area;
+    const auto t0 = std::chrono::steady_clock::now();
+    int cursor = 0;
+    bool seen = false;
+    for (uint32_t spin = 0;; spin++) {
+      if (rec_accept(rp, area, P.rec_tag, &cursor)) {
+        seen = true;
+        break;
+      }
+      if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
+      __builtin_ia32_pause();
+    }
+    if (!seen) {
+      HIP_TRY(hipStreamSynchronize(st));
+      if (!rec_accept(rp, area, P.rec_tag, &cursor))
+        return fail(PHIP_ERR_HIP, "record mode: block %d of %d stored no record for tag %u", cursor, rp.nblocks,
+                    P.rec_tag);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (host_trace) ht_reduce = hclock::now();
+    memset(P.pinned + 64, 0, (size_t)P.nmatch * 8);
+    rec_reduce(rp, P.rec_area, P.pinned, P.pinned + 32, P.pinned + 33, P.pinned + 64, P.rec_scratch.data());
   } else if (P.done_seq != 0 && !P.graph_exec && !P.select && !filter_words) {
     // the finalize kernel's completion word (Plan::done_seq): spin on the mapped result area; a kernel that has
     // not published within the bound is waited for on the stream (which also reports a failed launch)
@@ -5835,8 +5947,10 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (host_trace) {
     ht[4] = hclock::now();
     auto us = [&](int a, int b) { return std::chrono::duration<double, std::micro>(ht[b] - ht[a]).count(); };
-    fprintf(stderr, "phip_host_trace lane %.1f enqueue %.1f sync %.1f result %.1f total %.1f device %.1f\n", us(0, 1),
-            us(1, 2), us(2, 3), us(3, 4), us(0, 4), 1000.0 * r.device_ms);
+    const bool rec = P.rec_exec && mode == EXEC_FULL;
+    fprintf(stderr, "phip_host_trace lane %.1f enqueue %.1f sync %.1f result %.1f total %.1f device %.1f host_final %d reduce %.1f\n",
+            us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(0, 4), 1000.0 * r.device_ms, rec ? 1 : 0,
+            rec ? std::chrono::duration<double, std::micro>(ht[3] - ht_reduce).count() : 0.0);
   }
   return PHIP_OK;
 }

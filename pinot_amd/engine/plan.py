@@ -964,7 +964,8 @@ class GpuCombineOperator:
     def launch_shape(self):
         """The launch shape of the plan's last execution (phip_plan_launch_shape) as a dict of
         _lib.LAUNCH_SHAPE_FIELDS: work tiles, filter / aggregation workgroups, waves per aggregation workgroup, filter
-        ring slots, work-list segments and the distinct / selection grid caps; None before the plan exists."""
+        ring slots, work-list segments, the distinct / selection grid caps, fused_lean and host_final (1: the execution
+        reduced per-block records on the host instead of launching the finalize kernel); None before the plan exists."""
         if getattr(self, "_plan", None) is None:
             return None
         n = len(_lib.LAUNCH_SHAPE_FIELDS)
