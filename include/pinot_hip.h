@@ -331,7 +331,26 @@ typedef struct phip_query_desc {
   int32_t num_derived;
   int32_t reserved_derived;
   const phip_derived_column *derived;
+  /* Selection ORDER BY (SelectionOrderByOperator, pinot-core/.../operator/query/SelectionOrderByOperator.java, with
+   * SelectionOrderByCombineOperator): when num_select_order > 0 the result is the first select_keep (= offset + limit)
+   * rows of the matched docs sorted by the terms, each a select[] index with a direction: INT / LONG by value, FLOAT /
+   * DOUBLE and a op b in Double.compare order (-0.0 < 0.0, every NaN one value above +inf), dictionary STRING in the
+   * dictionaries' order. Rows equal on every term keep ascending (segment position in the query, doc id) order, so
+   * the rows are a stable sort of the selection-only rows. select[] holds the block's expressions, the ORDER BY
+   * expressions among them; select_limit is not read. At most 8 terms; a raw STRING term is PHIP_ERR_UNSUPPORTED.
+   * Statistics: numDocsScanned = the matched docs; numEntriesScannedPostFilter = matched x the distinct columns of
+   * the term expressions + sum over the segments of min(matched, select_keep) x the distinct columns only the other
+   * expressions read. All zero (as in every descriptor from before these fields) = no ORDER BY. */
+  int32_t num_select_order;
+  int32_t reserved_select_order;
+  const struct phip_select_order_term *select_order;
+  int64_t select_keep;
 } phip_query_desc;
+
+typedef struct phip_select_order_term {
+  int32_t select_index; /* index into phip_query_desc.select */
+  int32_t descending;
+} phip_select_order_term;
 
 typedef struct phip_select_expr {
   int32_t expr;     /* PHIP_EXPR_*: a column, or a op b (evaluated in double, as the transform functions do) */
@@ -624,7 +643,10 @@ PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *
 #define PHIP_SHAPE_FUSED_LEAN 8     /* 1: the filter launch was the lean fused instantiation (bit-sliced + deferred) */
 #define PHIP_SHAPE_HOST_FINAL 9     /* 1: the execution ran in record mode (tagged per-block records reduced on the host, no
                                      * finalize launch; PHIP_HOST_FINAL=0 at plan creation keeps the launch) */
-#define PHIP_LAUNCH_SHAPE_VALUES 10
+#define PHIP_SHAPE_SELECT_CANDIDATES 10 /* selection ORDER BY: the rows the top-K pruning pass left to gather and sort
+                                         * (select_keep <= candidates <= matched when matched >= select_keep, else
+                                         * = matched; saturates at INT32_MAX) */
+#define PHIP_LAUNCH_SHAPE_VALUES 11
 PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values);
 
 #endif /* PINOT_HIP_H_ */

@@ -57,7 +57,7 @@ EXCHANGE_HASH = 4
 
 # phip_plan_launch_shape values, in order (include/pinot_hip.h PHIP_SHAPE_*)
 LAUNCH_SHAPE_FIELDS = ("total_work", "filter_blocks", "agg_blocks", "agg_waves", "nbuf", "num_work_segments",
-                       "distinct_blocks", "select_blocks", "fused_lean", "host_final")
+                       "distinct_blocks", "select_blocks", "fused_lean", "host_final", "select_candidates")
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 
@@ -102,6 +102,11 @@ class SelectExpr(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class SelectOrderTerm(ctypes.Structure):
+    """phip_select_order_term: one ORDER BY term of a selection, over phip_query_desc.select."""
+    _fields_ = [("select_index", ctypes.c_int32), ("descending", ctypes.c_int32)]
+
+
 class ExprOp(ctypes.Structure):
     """phip_expr_op: one op of a derived value column's postfix program."""
     _fields_ = [("op", ctypes.c_int32), ("column", ctypes.c_int32), ("long_value", ctypes.c_int64),
@@ -127,7 +132,9 @@ class QueryDesc(ctypes.Structure):
                 ("num_select", ctypes.c_int32), ("stats_programs", ctypes.c_uint32),
                 ("select", ctypes.POINTER(SelectExpr)), ("select_limit", ctypes.c_int64),
                 ("num_derived", ctypes.c_int32), ("reserved_derived", ctypes.c_int32),
-                ("derived", ctypes.POINTER(DerivedColumn))]
+                ("derived", ctypes.POINTER(DerivedColumn)),
+                ("num_select_order", ctypes.c_int32), ("reserved_select_order", ctypes.c_int32),
+                ("select_order", ctypes.POINTER(SelectOrderTerm)), ("select_keep", ctypes.c_int64)]
 
 
 class Result(ctypes.Structure):

@@ -1,4 +1,4 @@
-// dev_common.h -- device helpers shared by the gfx950 kernels (filter.hip, aggregate.hip).
+// dev_common.h -- device helpers shared by the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -88,6 +88,14 @@ __host__ __device__ inline double f64_unordered(uint64_t u) {
   x.u = u;
   return x.d;
 }
+// The 64-bit order-preserving image of a double under Double.compare: the doubleToLongBits image (NaN canonical: a
+// SUM over a column holding 0xFFF8... carries the operand's sign bit, and the raw bits would put it below -inf),
+// negatives complemented, the others with the sign bit set.
+__device__ __forceinline__ uint64_t double_order(double d) {
+  const uint64_t u = d != d ? 0x7FF8000000000000ull : (uint64_t)__double_as_longlong(d);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
 __device__ __forceinline__ double as_f64(uint64_t u) { return __longlong_as_double((long long)u); }
 __device__ __forceinline__ uint64_t as_u64(double d) { return (uint64_t)__double_as_longlong(d); }
 

@@ -441,6 +441,33 @@ struct DevSelQuery {
   DevSelect sel[kMaxSelect];
 };
 
+// Selection ORDER BY (select_order.hip): SelectionOrderByOperator's top K = offset + limit rows. The matched docs are
+// pruned to a candidate set in one streaming pass over the primary term -- an 11-bit digit of its 64-bit order image
+// (sel_order_image), counted per digit; every doc at or below the digit at which the running count reaches K is a
+// candidate -- and only the candidates are gathered and sorted by the whole term list.
+constexpr int kMaxSelOrder = 8;                     // ORDER BY terms per selection
+constexpr int kSelOrderDigitBits = 11;
+constexpr int kSelOrderBins = 1 << kSelOrderDigitBits;
+struct DevSelOrder {
+  int32_t primary;       // the first term's select index
+  int32_t desc;          // ... descending: its image is complemented
+  uint64_t imin;         // host bound: no image of the primary term (after DESC) is below it ...
+  int32_t shift;         // ... and (image - imin) >> shift < kSelOrderBins (images outside the bound clamp)
+  int32_t prune;         // 0: every matched doc is a candidate (PHIP_SELECT_ORDER_PRUNE=0, measurement)
+  int64_t keep;          // K
+  uint64_t *bins;        // [kSelOrderBins] matched docs per digit, zeroed before the histogram pass
+  int64_t *bound;        // [2]: the boundary digit, the matched docs at or below it
+  uint32_t *cand_mask;   // [total_work][64] lane-major tile masks: matched and digit <= boundary
+};
+// One ORDER BY term over the gathered candidate columns (select_order_keys_kernel).
+struct SelOrderTerm {
+  int32_t sel;   // select index
+  int32_t kind;  // SelKind of that expression (SEL_I64 / SEL_F64 / SEL_ID)
+  int32_t desc;
+  int32_t bits;  // key bits to sort: ceil(log2 card) for ids, else 64
+  int64_t card;  // SEL_ID: the query-global cardinality (DESC keys are card - 1 - id)
+};
+
 // Exact DISTINCTCOUNT (distinct.hip): a pass of its own over the filter's tile masks that sets, per matched doc and
 // distinct slot, bit `global id` of the doc's group row in one device bitmap [num_rows][row_words] u32. A slot of kind
 // counts (PHIP_AGG_VALUE_COUNTS: PERCENTILE, MODE) holds a u32 count per global id in the same row instead.

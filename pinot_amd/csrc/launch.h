@@ -131,6 +131,22 @@ hipError_t launch_select_str_bytes(const uint64_t *loc, int64_t rows, const uint
 hipError_t launch_select_gather(const DevSelQuery *q, int64_t total_work, int max_blocks, uint64_t *out,
                                 int64_t num_rows, hipStream_t s);
 
+// ---- select_order.hip (selection ORDER BY) -----------------------------------------------------------------------
+// Registered like ExprLauncher below (null in the host simulation: an ORDER BY selection is PHIP_ERR_UNSUPPORTED).
+// hist / mask walk the work tiles as launch_select_count does; the runtime zeroes DevSelOrder.bins before hist. sort:
+// cols = the gathered candidates [num_select][n]; *scratch_bytes on a null scratch; *order_out = the candidates'
+// final order (in the scratch). rows: out[k][r] = cols[k][order[r]] for r < rows.
+struct SelectOrderLaunchers {
+  hipError_t (*hist)(const DevSelQuery *q, const DevSelOrder *o, int64_t total_work, int max_blocks, hipStream_t s);
+  hipError_t (*pick)(const DevSelOrder *o, hipStream_t s);
+  hipError_t (*mask)(const DevSelQuery *q, const DevSelOrder *o, int64_t total_work, int max_blocks, hipStream_t s);
+  hipError_t (*sort)(const uint64_t *cols, int64_t n, const SelOrderTerm *terms, int32_t num_terms, void *scratch,
+                     size_t *scratch_bytes, const int32_t **order_out, hipStream_t s);
+  hipError_t (*rows)(const uint64_t *cols, int64_t n, int32_t ncols, const int32_t *order, int64_t rows, uint64_t *out,
+                     hipStream_t s);
+};
+void register_select_order_launchers(const SelectOrderLaunchers *l);  // defined in runtime.cpp
+
 // ---- distinct.hip (exact DISTINCTCOUNT) --------------------------------------------------------------------------
 hipError_t launch_distinct_mark(const DevDistinctQuery *q, int64_t total_work, int lds, size_t lds_bytes,
                                 int max_blocks, hipStream_t s);

@@ -327,6 +327,8 @@ struct DerivedBuf {
 };
 // expr.hip's launcher (launch.h ExprLauncher): null in a library without the kernel unit (the host simulation)
 static phip::ExprLauncher g_expr_launcher = nullptr;
+// select_order.hip's launchers (launch.h SelectOrderLaunchers): null in a library without the kernel unit
+static const phip::SelectOrderLaunchers *g_sel_order = nullptr;
 static std::atomic<uint64_t> g_derived_clock{0};  // last-use stamps of the derived columns (least recently used first out)
 
 struct Segment {
@@ -2033,6 +2035,17 @@ struct Plan {
   std::vector<std::vector<const void *>> sel_str_ptrs;  // per SEL_STR expression: its segments' bytes, then offsets
   std::vector<int32_t> sel_bits, sel_width;  // per select column's projected bytes (algorithmic bytes)
   float sel_filter_ms = 0.f;
+  // selection ORDER BY (select_order.hip): the pruning pass's descriptor and the candidates' copy of the selection
+  // descriptor (its mask = the candidate masks, no per-segment limit) in the blob, their scratch, the terms
+  bool sel_ordered = false;
+  size_t so_off = 0, sq2_off = 0;
+  uint64_t *sel_bins = nullptr;  // [kSelOrderBins] then the two boundary words
+  int64_t *sel_tile_cnt2 = nullptr, *sel_tile_off2 = nullptr, *sel_base2 = nullptr, *sel_kept2 = nullptr,
+          *sel_total2 = nullptr;
+  std::vector<SelOrderTerm> sel_terms;
+  int64_t sel_keep = 0;
+  int sel_order_cols = 0, sel_rest_cols = 0;  // distinct columns of the term expressions / of the others alone
+  int64_t sel_candidates = 0;                 // of the last execution (phip_plan_launch_shape)
   // exact DISTINCTCOUNT and value counts (distinct.hip): slot s = the plan's s-th PHIP_AGG_DISTINCT or
   // PHIP_AGG_VALUE_COUNTS aggregation (dist_agg[s]); the
   // descriptor in the blob, the bitmap [dense key space][row words] cleared and filled by every execution
@@ -2287,6 +2300,7 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
 // derived value columns (include/pinot_hip.h phip_expr_op; expr.hip)
 // ================================================================================================
 void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
+void phip::register_select_order_launchers(const SelectOrderLaunchers *l) { g_sel_order = l; }
 // the filter kernels of this library store records (filter.hip registers it; false in a build without the kernel units,
 // whose stand-in launch_filter knows nothing of records)
 static bool g_filter_records = false;
@@ -3152,6 +3166,113 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   }
   sq.num_select = nsel;
   sq.limit = std::max<int64_t>(0, q->select_limit);
+  // selection ORDER BY (SelectionOrderByOperator): the terms over select[], the primary term's digit bound
+  const int nord = q->num_select_order;
+  DevSelOrder so;
+  memset(&so, 0, sizeof(so));
+  std::vector<SelOrderTerm> sel_terms;
+  int sel_order_cols = 0, sel_rest_cols = 0;
+  if (nord < 0 || (nord > 0 && (nsel == 0 || !q->select_order)))
+    return fail(PHIP_ERR_INVALID, "selection ORDER BY: terms without select expressions");
+  if (nord > kMaxSelOrder) return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: at most %d terms", kMaxSelOrder);
+  if (nord > 0) {
+    if (!g_sel_order) return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: this library has no select_order kernels");
+    if (q->select_keep <= 0) return fail(PHIP_ERR_INVALID, "selection ORDER BY: select_keep must be positive");
+    std::vector<bool> in_order(ncols, false), in_rest(ncols, false);
+    std::vector<bool> is_term(nsel, false);
+    for (int j = 0; j < nord; j++) {
+      const int k = q->select_order[j].select_index;
+      if (k < 0 || k >= nsel) return fail(PHIP_ERR_INVALID, "selection ORDER BY: term %d names no select expression", j);
+      const DevSelect &d = sq.sel[k];
+      if (d.kind == SEL_STR)
+        return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: raw STRING column %s as a term", q->columns[d.col_a]);
+      SelOrderTerm t;
+      t.sel = k;
+      t.kind = d.kind;
+      t.desc = q->select_order[j].descending ? 1 : 0;
+      t.card = d.kind == SEL_ID ? std::max<int64_t>(1, sel_dicts[k]->card) : 0;
+      t.bits = 64;
+      if (d.kind == SEL_ID) {
+        // the query-global dictionary is in padded-byte order (compare_value): String.compareTo's only below U+E000
+        for (uint8_t b : sel_dicts[k]->values)
+          if (b >= 0xEE)
+            return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: STRING column %s holds a character at or above U+E000",
+                        q->columns[d.col_a]);
+        for (t.bits = 1; t.bits < 63 && ((int64_t)1 << t.bits) < t.card; t.bits++) {
+        }
+      }
+      sel_terms.push_back(t);
+      is_term[k] = true;
+    }
+    for (int k = 0; k < nsel; k++)
+      for (int c : {sq.sel[k].col_a, sq.sel[k].col_b}) (is_term[k] ? in_order : in_rest)[c] = true;
+    for (int c = 0; c < ncols; c++) {
+      sel_order_cols += in_order[c] ? 1 : 0;
+      sel_rest_cols += in_rest[c] && !in_order[c] ? 1 : 0;
+    }
+    // the primary term's images lie in [lo, hi]: ids by the cardinality, INT / LONG by the segments' value ranges,
+    // dictionary FLOAT / DOUBLE by the dictionaries' ends, else every image (a digit outside the bound clamps)
+    const SelOrderTerm &t0 = sel_terms[0];
+    const DevSelect &d0 = sq.sel[t0.sel];
+    const uint64_t sign = 0x8000000000000000ull;
+    auto dbl_image = [](double v) -> uint64_t {  // dev_common.h double_order
+      uint64_t u = 0x7FF8000000000000ull;
+      if (v == v) memcpy(&u, &v, 8);
+      return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    };
+    uint64_t lo = 0, hi = ~0ull;
+    if (d0.kind == SEL_ID) {
+      lo = sign;
+      hi = (uint64_t)(t0.card - 1) ^ sign;
+    } else if (d0.expr == PHIP_EXPR_COLUMN) {
+      bool known = true;
+      uint64_t l = ~0ull, h = 0;
+      for (int s = 0; s < nseg && known; s++) {
+        const ColumnStore &cs = segs[s]->cols[colidx[s][d0.col_a]];
+        if (d0.kind == SEL_I64 && cs.has_range) {
+          l = std::min(l, (uint64_t)cs.vmin ^ sign);
+          h = std::max(h, (uint64_t)cs.vmax ^ sign);
+        } else if (d0.kind == SEL_F64 && !no_dict(cs) && cs.card > 0 &&
+                   cs.host_dict.size() == (size_t)cs.card * type_width(cs.type)) {
+          const int w = type_width(cs.type);
+          for (size_t i : {(size_t)0, (size_t)cs.card - 1}) {
+            double v;
+            if (w == 4) {
+              const uint32_t u = be32(cs.host_dict.data() + i * 4);
+              float f;
+              memcpy(&f, &u, 4);
+              v = f;
+            } else {
+              const uint64_t u = be64(cs.host_dict.data() + i * 8);
+              memcpy(&v, &u, 8);
+            }
+            l = std::min(l, dbl_image(v));
+            h = std::max(h, dbl_image(v));
+          }
+        } else {
+          known = false;
+        }
+      }
+      if (known && l <= h) {
+        lo = l;
+        hi = h;
+      }
+    }
+    if (t0.desc) {
+      const uint64_t l = ~hi, h = ~lo;
+      lo = l;
+      hi = h;
+    }
+    so.primary = t0.sel;
+    so.desc = t0.desc;
+    so.imin = lo;
+    for (so.shift = 0; ((hi - lo) >> so.shift) >= (uint64_t)kSelOrderBins; so.shift++) {
+    }
+    const char *pr = getenv("PHIP_SELECT_ORDER_PRUNE");  // measurement: 0 = every matched doc is a candidate
+    so.prune = pr && atoi(pr) == 0 ? 0 : 1;
+    so.keep = q->select_keep;
+    sq.limit = INT64_MAX;  // the ranks are those of all matched docs
+  }
   int num_projected = 0;
   {
     std::vector<bool> counted = projected;  // (tuple keys: the query's own group-by columns are the projected ones)
@@ -4399,6 +4520,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   const size_t kinds_off = blob.add(kinds.data(), kinds.size() * 4);
   const size_t dq_off = blob.reserve(sizeof(DevAggQuery));  // written once every pointer is known
   const size_t sq_off = nsel > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
+  const size_t sq2_off = nord > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
+  const size_t so_off = nord > 0 ? blob.reserve(sizeof(DevSelOrder)) : 0;
   const size_t dstq_off = ndist > 0 ? blob.reserve(sizeof(DevDistinctQuery)) : 0;
 
   void *dblob;
@@ -4549,6 +4672,36 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     sq.tile_off = P.sel_tile_off;
     sq.seg_base = P.sel_base;
     memcpy(blob.data.data() + sq_off, &sq, sizeof(sq));
+    if (nord > 0) {
+      // the candidates' chain: its own tile counts, ranks and bases over the candidate masks, every candidate kept
+      void *ob, *cm;
+      rc = P.alloc((size_t)kSelOrderBins * 8 + 16 + ((size_t)total_work + 1) * 16 + (2 * nent + 1) * 8 + 16, &ob);
+      if (rc) return rc;
+      rc = P.alloc(std::max<size_t>((size_t)total_work, 1) * 64 * 4, &cm);
+      if (rc) return rc;
+      P.sel_bins = (uint64_t *)ob;
+      P.sel_tile_cnt2 = (int64_t *)(P.sel_bins + kSelOrderBins + 2);
+      P.sel_tile_off2 = P.sel_tile_cnt2 + total_work + 1;
+      P.sel_base2 = P.sel_tile_off2 + total_work + 1;
+      P.sel_kept2 = P.sel_base2 + nent + 1;
+      P.sel_total2 = P.sel_kept2 + nent;
+      so.bins = P.sel_bins;
+      so.bound = (int64_t *)(P.sel_bins + kSelOrderBins);
+      so.cand_mask = (uint32_t *)cm;
+      DevSelQuery sq2 = sq;
+      sq2.mask = so.cand_mask;
+      sq2.tile_off = P.sel_tile_off2;
+      sq2.seg_base = P.sel_base2;
+      memcpy(blob.data.data() + sq2_off, &sq2, sizeof(sq2));
+      memcpy(blob.data.data() + so_off, &so, sizeof(so));
+      P.sel_ordered = true;
+      P.sq2_off = sq2_off;
+      P.so_off = so_off;
+      P.sel_terms = sel_terms;
+      P.sel_keep = so.keep;
+      P.sel_order_cols = sel_order_cols;
+      P.sel_rest_cols = sel_rest_cols;
+    }
     P.select = true;
     P.nsel = nsel;
     P.sq_off = sq_off;
@@ -5149,6 +5302,119 @@ static int32_t group_limit(Plan &P, Workspace &ws, hipStream_t st, int64_t match
   return PHIP_OK;
 }
 
+// Raw STRING expressions of a selection: `out` = the rows' 8-byte slots on the device, column-major [nsel][rows], a
+// SEL_STR column holding row locators; impl.sel_values the same slots on the host.
+static int32_t select_raw_strings(Plan &P, Workspace &ws, hipStream_t st, ResultImpl &impl, const void *out,
+                                  int64_t rows) {
+  int32_t rc;
+  // raw STRING expressions: the rows' bytes gathered by locator, then the distinct row values (bytewise order) as
+  // this result's dictionary of the column, the rows pointing into it
+  for (int k = 0; k < P.nsel; k++) {
+    if (P.sel_str_ptrs[k].empty()) continue;
+    const std::vector<const void *> &ptrs = P.sel_str_ptrs[k];
+    const size_t ns = ptrs.size() / 2;
+    void *tab, *lens, *doff, *dst;
+    if ((rc = ws.get("sel_str_tab", ptrs.size() * 8, &tab)) || (rc = ws.get("sel_str_lens", (size_t)rows * 4, &lens)) ||
+        (rc = ws.get("sel_str_off", (size_t)rows * 8, &doff)))
+      return rc;
+    const uint64_t *loc = (const uint64_t *)out + (size_t)k * rows;
+    HIP_TRY(hipMemcpyAsync(tab, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_select_str_lens(loc, rows, (const uint64_t *const *)tab + ns, (uint32_t *)lens, st));
+    std::vector<uint32_t> hl((size_t)rows);
+    HIP_TRY(hipMemcpyAsync(hl.data(), lens, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<uint64_t> ho((size_t)rows + 1, 0);
+    for (int64_t r = 0; r < rows; r++) ho[(size_t)r + 1] = ho[(size_t)r] + hl[(size_t)r];
+    if ((rc = ws.get("sel_str_bytes", std::max<uint64_t>(ho[(size_t)rows], 16), &dst))) return rc;
+    HIP_TRY(hipMemcpyAsync(doff, ho.data(), (size_t)rows * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_select_str_bytes(loc, rows, (const uint8_t *const *)tab, (const uint64_t *const *)tab + ns,
+                                    (const uint64_t *)doff, (uint8_t *)dst, st));
+    std::vector<uint8_t> hb(ho[(size_t)rows]);
+    if (!hb.empty()) HIP_TRY(hipMemcpyAsync(hb.data(), dst, hb.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<std::string> vals((size_t)rows);
+    for (int64_t r = 0; r < rows; r++) vals[(size_t)r].assign((const char *)hb.data() + ho[(size_t)r], hl[(size_t)r]);
+    std::vector<std::string> uniq = vals;
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    size_t width = 1;
+    for (const auto &u : uniq) width = std::max(width, u.size());
+    auto rd = std::make_shared<Device::Remap>();
+    rd->type = PHIP_TYPE_STRING;
+    rd->width = (int32_t)width;
+    rd->card = (int32_t)uniq.size();
+    rd->values.assign(uniq.size() * width, 0);
+    for (size_t i = 0; i < uniq.size(); i++) memcpy(rd->values.data() + i * width, uniq[i].data(), uniq[i].size());
+    for (int64_t r = 0; r < rows; r++)
+      impl.sel_values[(size_t)k * rows + r] =
+          (uint64_t)(std::lower_bound(uniq.begin(), uniq.end(), vals[(size_t)r]) - uniq.begin());
+    impl.sel_dicts[k] = rd;
+  }
+  return PHIP_OK;
+}
+
+// Selection ORDER BY (select_order.hip): rank the matched docs (kept[e] = entry e's matched docs), prune them to the
+// candidates in one pass over the primary term, gather the candidates in (segment, doc) order, sort them by the
+// terms and keep the first K rows. Two waits: the candidate count (the allocations need it), then the rows.
+static int32_t execute_select_ordered(Plan &P, Workspace &ws, hipStream_t st, ResultImpl &impl,
+                                      std::vector<int64_t> &kept, int64_t *num_rows, float *gather_ms) {
+  const DevSelQuery *dsq = (const DevSelQuery *)(P.base + P.sq_off), *dsq2 = (const DevSelQuery *)(P.base + P.sq2_off);
+  const DevSelOrder *dso = (const DevSelOrder *)(P.base + P.so_off);
+  const SelectOrderLaunchers &L = *g_sel_order;
+  const int64_t tw = P.total_work;
+  const size_t nent = P.dsegs.size();
+  int32_t rc;
+  int64_t tot[2] = {0, 0};
+  P.sel_candidates = 0;
+  if (tw > 0) {
+    size_t tb = 0;
+    HIP_TRY(launch_select_scan(nullptr, &tb, nullptr, nullptr, tw + 1, st));
+    void *tmp;
+    if ((rc = ws.get("sel_scan", std::max<size_t>(tb, 16), &tmp))) return rc;
+    HIP_TRY(launch_select_count(dsq, tw, P.sel_max_blocks, P.sel_tile_cnt, st));
+    HIP_TRY(launch_select_scan(tmp, &tb, P.sel_tile_cnt, P.sel_tile_off, tw + 1, st));
+    HIP_TRY(launch_select_bases(dsq, P.sel_base, P.sel_kept, P.sel_total, st));
+    if ((rc = check_deadline(P, "before the ORDER BY pruning pass"))) return rc;
+    HIP_TRY(hipMemsetAsync(P.sel_bins, 0, ((size_t)kSelOrderBins + 2) * 8, st));
+    HIP_TRY(L.hist(dsq, dso, tw, P.sel_max_blocks, st));
+    HIP_TRY(L.pick(dso, st));
+    HIP_TRY(L.mask(dsq, dso, tw, P.sel_max_blocks, st));
+    HIP_TRY(launch_select_count(dsq2, tw, P.sel_max_blocks, P.sel_tile_cnt2, st));
+    HIP_TRY(launch_select_scan(tmp, &tb, P.sel_tile_cnt2, P.sel_tile_off2, tw + 1, st));
+    HIP_TRY(launch_select_bases(dsq2, P.sel_base2, P.sel_kept2, P.sel_total2, st));
+    HIP_TRY(hipMemcpyAsync(tot, P.sel_total2, 16, hipMemcpyDeviceToHost, st));
+    if (nent) HIP_TRY(hipMemcpyAsync(kept.data(), P.sel_kept, nent * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t cand = tot[1];
+  if (cand > INT32_MAX) return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: %lld candidate rows", (long long)cand);
+  P.sel_candidates = cand;
+  const int64_t rows = std::min(cand, P.sel_keep);
+  const size_t nsel = (size_t)P.nsel;
+  impl.sel_values.assign((size_t)rows * nsel, 0);
+  if (rows > 0) {
+    if ((rc = check_deadline(P, "before the ORDER BY sort"))) return rc;
+    void *cols, *out, *scratch;
+    size_t sb = 0;
+    HIP_TRY(L.sort(nullptr, cand, P.sel_terms.data(), (int32_t)P.sel_terms.size(), nullptr, &sb, nullptr, st));
+    if ((rc = ws.get("sel_cand", (size_t)cand * nsel * 8, &cols)) || (rc = ws.get("sel_out", (size_t)rows * nsel * 8, &out)) ||
+        (rc = ws.get("sel_sort", std::max<size_t>(sb, 16), &scratch)))
+      return rc;
+    HIP_TRY(hipEventRecord(P.ev[4], st));
+    HIP_TRY(launch_select_gather(dsq2, tw, P.sel_max_blocks, (uint64_t *)cols, cand, st));
+    const int32_t *order = nullptr;
+    HIP_TRY(L.sort((const uint64_t *)cols, cand, P.sel_terms.data(), (int32_t)P.sel_terms.size(), scratch, &sb, &order, st));
+    HIP_TRY(L.rows((const uint64_t *)cols, cand, P.nsel, order, rows, (uint64_t *)out, st));
+    HIP_TRY(hipEventRecord(P.ev[2], st));
+    HIP_TRY(hipMemcpyAsync(impl.sel_values.data(), out, (size_t)rows * nsel * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(gather_ms, P.ev[4], P.ev[2]));
+    if ((rc = select_raw_strings(P, ws, st, impl, out, rows))) return rc;
+  }
+  *num_rows = rows;
+  return PHIP_OK;
+}
+
 // Selection (select.hip): after the filter launch, rank the matched docs per work tile, give each entry its rows
 // (first LIMIT in doc order, concatenated in segment order up to LIMIT) and gather the select expressions.
 // Blocks until the rows are in impl.sel_values; kept[e] receives each entry's kept rows (numDocsScanned).
@@ -5170,6 +5436,7 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     rd->width = 1;
     impl.sel_dicts[k] = rd;
   }
+  if (P.sel_ordered) return execute_select_ordered(P, ws, st, impl, kept, num_rows, gather_ms);
   if (tw > 0) {
     size_t tb = 0;
     HIP_TRY(launch_select_scan(nullptr, &tb, nullptr, nullptr, tw + 1, st));
@@ -5193,49 +5460,7 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     HIP_TRY(hipMemcpyAsync(impl.sel_values.data(), out, (size_t)rows * P.nsel * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipEventElapsedTime(gather_ms, P.ev[4], P.ev[2]));
-    // raw STRING expressions: the rows' bytes gathered by locator, then the distinct row values (bytewise order) as
-    // this result's dictionary of the column, the rows pointing into it
-    for (int k = 0; k < P.nsel; k++) {
-      if (P.sel_str_ptrs[k].empty()) continue;
-      const std::vector<const void *> &ptrs = P.sel_str_ptrs[k];
-      const size_t ns = ptrs.size() / 2;
-      void *tab, *lens, *doff, *dst;
-      if ((rc = ws.get("sel_str_tab", ptrs.size() * 8, &tab)) || (rc = ws.get("sel_str_lens", (size_t)rows * 4, &lens)) ||
-          (rc = ws.get("sel_str_off", (size_t)rows * 8, &doff)))
-        return rc;
-      const uint64_t *loc = (const uint64_t *)out + (size_t)k * rows;
-      HIP_TRY(hipMemcpyAsync(tab, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(launch_select_str_lens(loc, rows, (const uint64_t *const *)tab + ns, (uint32_t *)lens, st));
-      std::vector<uint32_t> hl((size_t)rows);
-      HIP_TRY(hipMemcpyAsync(hl.data(), lens, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      std::vector<uint64_t> ho((size_t)rows + 1, 0);
-      for (int64_t r = 0; r < rows; r++) ho[(size_t)r + 1] = ho[(size_t)r] + hl[(size_t)r];
-      if ((rc = ws.get("sel_str_bytes", std::max<uint64_t>(ho[(size_t)rows], 16), &dst))) return rc;
-      HIP_TRY(hipMemcpyAsync(doff, ho.data(), (size_t)rows * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(launch_select_str_bytes(loc, rows, (const uint8_t *const *)tab, (const uint64_t *const *)tab + ns,
-                                      (const uint64_t *)doff, (uint8_t *)dst, st));
-      std::vector<uint8_t> hb(ho[(size_t)rows]);
-      if (!hb.empty()) HIP_TRY(hipMemcpyAsync(hb.data(), dst, hb.size(), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      std::vector<std::string> vals((size_t)rows);
-      for (int64_t r = 0; r < rows; r++) vals[(size_t)r].assign((const char *)hb.data() + ho[(size_t)r], hl[(size_t)r]);
-      std::vector<std::string> uniq = vals;
-      std::sort(uniq.begin(), uniq.end());
-      uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-      size_t width = 1;
-      for (const auto &u : uniq) width = std::max(width, u.size());
-      auto rd = std::make_shared<Device::Remap>();
-      rd->type = PHIP_TYPE_STRING;
-      rd->width = (int32_t)width;
-      rd->card = (int32_t)uniq.size();
-      rd->values.assign(uniq.size() * width, 0);
-      for (size_t i = 0; i < uniq.size(); i++) memcpy(rd->values.data() + i * width, uniq[i].data(), uniq[i].size());
-      for (int64_t r = 0; r < rows; r++)
-        impl.sel_values[(size_t)k * rows + r] =
-            (uint64_t)(std::lower_bound(uniq.begin(), uniq.end(), vals[(size_t)r]) - uniq.begin());
-      impl.sel_dicts[k] = rd;
-    }
+    if ((rc = select_raw_strings(P, ws, st, impl, out, rows))) return rc;
   }
   *num_rows = rows;
   return PHIP_OK;
@@ -5352,7 +5577,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (mode != EXEC_FINISH) {
     const int32_t sh[PHIP_LAUNCH_SHAPE_VALUES] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves,
                                                   P.fq.nbuf, (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks,
-                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0};
+                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0, 0};
     memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {
@@ -5768,6 +5993,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     float t_f = 0.f;
     HIP_TRY(hipEventElapsedTime(&t_f, P.ev[1], P.ev[4]));  // the filter launch, before the events are reused
     if ((rc = execute_select(P, ws, st, *impl, sel_kept, &sel_rows, &sel_ms))) return rc;
+    P.shape[PHIP_SHAPE_SELECT_CANDIDATES] = (int32_t)std::min<int64_t>(P.sel_candidates, INT32_MAX);
     P.sel_filter_ms = t_f;
   }
   const int64_t matched = has_filter ? (int64_t)fin[32] : docs_in_work;
@@ -5902,6 +6128,13 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     }
     r.num_docs_scanned = docs;
     r.num_entries_scanned_post_filter = docs * P.num_projected;
+    if (P.sel_ordered) {
+      // SelectionOrderByOperator: every matched doc reads the term expressions' columns (sel_kept = the matched docs),
+      // the rows a segment keeps (at most K) the columns only the other expressions read
+      int64_t kept_rows = 0;
+      for (int s = 0; s < nseg; s++) kept_rows += std::min(per_seg[s], P.sel_keep);
+      r.num_entries_scanned_post_filter = docs * P.sel_order_cols + kept_rows * P.sel_rest_cols;
+    }
     r.num_segments_matched = segs_matched;
     r.num_rows = sel_rows;
     r.num_select = P.nsel;

@@ -15,14 +15,6 @@
 
 namespace phip {
 
-// The 64-bit order-preserving image of a double under Double.compare: the doubleToLongBits image (NaN canonical: a
-// SUM over a column holding 0xFFF8... carries the operand's sign bit, and the raw bits would put it below -inf),
-// negatives complemented, the others with the sign bit set.
-__device__ __forceinline__ uint64_t double_order(double d) {
-  const uint64_t u = d != d ? 0x7FF8000000000000ull : (uint64_t)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 __global__ void order_keys_kernel(const double *__restrict__ vals, int64_t n, int32_t naggs, int32_t agg, int32_t desc,
                                   uint64_t *__restrict__ ukeys, int32_t *__restrict__ idx) {
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (int64_t)gridDim.x * blockDim.x) {

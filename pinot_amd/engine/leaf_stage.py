@@ -190,7 +190,11 @@ class GpuLeafStageOperator:
                 exprs = [e for e, _ in self.query.select]
                 if len(exprs) == 1 and str(exprs[0]) == "*":
                     exprs = list(blk.column_names)
-                return compose_select_transferable_block(blk, exprs, self.desired or block_schema(blk))
+                # (an ORDER BY selection's block leads with its order-by expressions: the default schema is the
+                # select list's, each column looked up by its expression's name)
+                pos = {n: i for i, n in enumerate(blk.column_names)}
+                own = DataSchema([str(e) for e in exprs], [blk.column_types[pos[str(e)]] for e in exprs])
+                return compose_select_transferable_block(blk, exprs, self.desired or own)
             return compose_transferable_block(blk, self.desired or block_schema(blk))
         self._state = 2
         return TransferableBlock(None, None, is_end_of_stream=True, stats=dict(self._stats))

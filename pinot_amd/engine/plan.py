@@ -1365,14 +1365,41 @@ class GpuSelectionOperator(GpuCombineOperator):
     query-global dictionary. Statistics as the reference's: numDocsScanned = the rows each segment kept,
     numEntriesScannedPostFilter = that x the projected columns. numEntriesScannedInFilter is the full filter scan
     (the reference's lazy scan stops at LIMIT; the known answers exclude it). LIMIT 0 is EmptySelectionOperator:
-    the schema, no rows, zero statistics. ORDER BY (SelectionOrderByOperator) is outside this operator."""
+    the schema, no rows, zero statistics.
+
+    With ORDER BY (and LIMIT > 0) this is SelectionOrderByOperator (…/operator/query/SelectionOrderByOperator.java)
+    with SelectionOrderByCombineOperator's merge: the block's columns are the order-by expressions, deduplicated in
+    ORDER BY order, then the select expressions not among them (QueryContext.selection_block_expressions); its rows
+    the best K = OFFSET + LIMIT of all matched docs under the comparator -- INT / LONG by value, FLOAT / DOUBLE and
+    a op b in Double.compare order (-0.0 < 0.0, every NaN equal and above +inf), dictionary STRING in
+    String.compareTo order -- sorted. Which of the rows equal on every term the reference keeps is heap- and
+    thread-timing dependent; here they keep ascending (segment position in the query, doc id) order, so the rows are
+    the first K of a stable sort of the selection-only rows. The device prunes the matched docs to a candidate set in
+    one pass over the first term and sorts only those (select_order.hip). Statistics: numDocsScanned = every matched
+    doc; numEntriesScannedPostFilter = matched x the distinct columns of the order-by expressions + per segment
+    min(matched, K) x the distinct columns only the other expressions read. Refused (UnsupportedOnGpu): a first
+    order-by column that is sorted in a segment (SelectionPartiallyOrderedByAsc/DescOperator stop early and count
+    differently), a raw STRING order-by column, a STRING order-by dictionary with a character at or above U+E000
+    (the dictionaries are in UTF-8 byte order, which is String.compareTo's only below), more than 8 terms."""
+
+    _MAX_ORDER_TERMS = 8  # device.h kMaxSelOrder
 
     def __init__(self, query: QueryContext, segments: Sequence[GpuSegment], num_groups_limit: int = 0):
-        if query.order_by and query.limit > 0:
-            raise UnsupportedOnGpu("selection ORDER BY (SelectionOrderByOperator)")
         if not segments:
             raise UnsupportedOnGpu("selection over no segments")
-        self.exprs = query.select_expressions(list(segments[0].segment.columns))
+        self.ordered = bool(query.order_by) and query.limit > 0
+        if query.offset and not self.ordered:
+            raise UnsupportedOnGpu("OFFSET on a query that is not an ORDER BY selection (the broker's to apply)")
+        self.exprs = query.selection_block_expressions(list(segments[0].segment.columns))
+        self.order_terms = []  # (block expression index, descending)
+        if self.ordered:
+            if len(query.order_by) > self._MAX_ORDER_TERMS:
+                raise UnsupportedOnGpu(f"selection ORDER BY of more than {self._MAX_ORDER_TERMS} terms")
+            for j, ob in enumerate(query.order_by):
+                e = _strip_cast(ob.expression)
+                if isinstance(e, Identifier):
+                    self._check_order_column(e.name, segments, first=j == 0)
+                self.order_terms.append((self.exprs.index(ob.expression), not ob.ascending))
         self.sel = []
         for e in self.exprs:
             e2 = _strip_cast(e)
@@ -1400,9 +1427,36 @@ class GpuSelectionOperator(GpuCombineOperator):
             else:
                 self.types.append("DOUBLE")
 
+    @staticmethod
+    def _check_order_column(name, segments, first):
+        for s in segments:
+            if not s.has_column(name):
+                raise KeyError(f"segment {s.name} has no column {name}")
+            m = s.column_metadata(name)
+            if first and m.is_sorted:
+                raise UnsupportedOnGpu(f"selection ORDER BY: first column {name} is sorted in segment {s.name} "
+                                       "(SelectionPartiallyOrderedByAsc/DescOperator)")
+            if m.data_type != DataType.STRING:
+                continue
+            if not m.has_dictionary:
+                raise UnsupportedOnGpu(f"selection ORDER BY over the raw (no-dictionary) STRING column {name}")
+            raw = np.frombuffer(s.segment.columns[name].dictionary, dtype=np.uint8)
+            if len(raw) and int(raw.max()) >= 0xEE:
+                raise UnsupportedOnGpu(f"selection ORDER BY: STRING column {name} holds a character at or above "
+                                       "U+E000 (byte order is String.compareTo order only below it)")
+
     def _desc(self, keep):
         q = super()._desc(keep)
         col_index = {c: i for i, c in enumerate(self.columns)}
+        if self.ordered:
+            terms = (_lib.SelectOrderTerm * len(self.order_terms))()
+            for j, (k, desc) in enumerate(self.order_terms):
+                terms[j].select_index = k
+                terms[j].descending = int(desc)
+            keep.append(terms)
+            q.num_select_order = len(self.order_terms)
+            q.select_order = terms
+            q.select_keep = int(self.query.offset) + int(self.query.limit)
         arr = (_lib.SelectExpr * len(self.sel))()
         for i, (expr, a, b) in enumerate(self.sel):
             arr[i].expr = expr
@@ -2211,6 +2265,8 @@ def _null_handling_operator(query: QueryContext, segments, limit):
     if query.is_selection:
         if null_cols([e for e, _ in query.select]):
             raise UnsupportedOnGpu("enableNullHandling: selected columns with null values")
+        if null_cols([ob.expression for ob in query.order_by]):
+            raise UnsupportedOnGpu("enableNullHandling: order-by columns with null values")
         return None
     nullable_args = [ag.argument for ag in query.aggregations if ag.function in _NULLABLE and ag.argument is not None]
     if query.group_by:
@@ -2538,6 +2594,8 @@ class GpuInstancePlanMaker:
         from .startree import GpuStarTreeOperator
         limit = int(query.options["numGroupsLimit"]) if "numGroupsLimit" in query.options and query.group_by \
             else self.num_groups_limit
+        if query.offset and not (query.is_selection and query.order_by and query.limit > 0):
+            raise UnsupportedOnGpu("OFFSET on a query that is not an ORDER BY selection (the broker's to apply)")
         if null_handling_enabled(query):
             op = _null_handling_operator(query, segments, limit)
             if op is not None:

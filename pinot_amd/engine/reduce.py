@@ -188,6 +188,8 @@ def reduce_blocks(query: QueryContext, blocks) -> ResultTable:
     for b in blocks:
         stats.merge(b.stats)
     if query.is_selection:
+        if query.order_by and query.limit > 0:
+            return _reduce_selection_order_by(query, blocks, stats)
         return _reduce_selection(query, blocks, stats)
     names = [_column_name(e, a, query) for e, a in query.select]
     if not query.group_by:
@@ -258,6 +260,39 @@ def _reduce_selection(query: QueryContext, blocks, stats) -> ResultTable:
                 break
             rows.append([r[i] for i in picks])
     return ResultTable(names, rows, stats)
+
+
+def selection_order_value(v):
+    """A selection value as Python orders it like the reference's comparator: a float by Double.compare
+    (double_order), a string by String.compareTo (UTF-16 code units), an integer by value."""
+    if isinstance(v, (float, np.floating)):
+        return double_order(float(v))
+    if isinstance(v, str):
+        return v.encode("utf-16-be")
+    return int(v)
+
+
+def _reduce_selection_order_by(query: QueryContext, blocks, stats) -> ResultTable:
+    """SelectionOrderByReducer (the broker's selection-order-by reduce, SelectionOperatorService): the servers' sorted
+    blocks merged by the comparator -- rows equal on every term keep the blocks' order, then each block's own -- the
+    first OFFSET rows skipped, LIMIT kept, each row mapped from the block's columns (order-by expressions first) to the
+    select list; SELECT * keeps the block's schema order, as _reduce_selection does."""
+    schema = next((b for b in blocks if b.column_names), None)
+    if schema is None:
+        return ResultTable([], [], stats)
+    index = {n: i for i, n in enumerate(schema.column_names)}
+    star = len(query.select) == 1 and str(query.select[0][0]) == "*"
+    if star:
+        names, picks = list(schema.column_names), list(range(len(schema.column_names)))
+    else:
+        names = [_column_name(e, a, query) for e, a in query.select]
+        picks = [index[str(e)] for e, _ in query.select]
+    rows = [r for b in blocks for r in b.rows]
+    for ob in reversed(query.order_by):  # (list.sort is stable, with reverse too: equal rows keep their order)
+        i = index[str(ob.expression)]
+        rows.sort(key=lambda r: selection_order_value(r[i]), reverse=not ob.ascending)
+    rows = rows[query.offset:query.offset + query.limit]
+    return ResultTable(names, [[r[i] for i in picks] for r in rows], stats)
 
 
 def trim_size(query: QueryContext, min_trim=None) -> int:

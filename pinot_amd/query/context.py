@@ -251,6 +251,7 @@ class QueryContext:
     order_by: List[OrderByExpression] = field(default_factory=list)
     limit: int = 10
     options: dict = field(default_factory=dict)
+    offset: int = 0
 
     @property
     def is_aggregation(self) -> bool:
@@ -274,6 +275,21 @@ class QueryContext:
             return [Identifier(c) for c in sorted(c for c in (segment_columns or []) if not c.startswith("$"))]
         out = []
         for e in exprs:
+            if e not in out:
+                out.append(e)
+        return out
+
+    def selection_block_expressions(self, segment_columns=None):
+        """SelectionOperatorUtils.extractExpressions (SelectionOperatorUtils.java:83-124) with ORDER BY: the order-by
+        expressions first, deduplicated in ORDER BY order, then the select expressions not among them in select order
+        (SELECT * = the segment's columns sorted by name, '$' columns excluded). Without ORDER BY, or with LIMIT 0
+        (which ignores it), select_expressions."""
+        out = []
+        if self.limit > 0:
+            for ob in self.order_by:
+                if ob.expression not in out:
+                    out.append(ob.expression)
+        for e in self.select_expressions(segment_columns):
             if e not in out:
                 out.append(e)
         return out

@@ -3,7 +3,7 @@
 The reference compiles SQL with Calcite (CalciteSqlParser, pinot-common/.../sql/parsers/) into a
 PinotQuery, then QueryContextConverterUtils builds a QueryContext. This is a recursive-descent
 parser for the subset the parity tests and SSB use: SELECT <aggregations / group columns>
-FROM t [WHERE <boolean expr>] [GROUP BY ...] [ORDER BY ...] [LIMIT n], with predicates
+FROM t [WHERE <boolean expr>] [GROUP BY ...] [ORDER BY ...] [LIMIT n [OFFSET m] | LIMIT m, n], with predicates
 =, <>, !=, <, <=, >, >=, [NOT] BETWEEN, [NOT] IN, IS [NOT] NULL and NOT/AND/OR, and +, -, *, / and CAST in
 expressions. The reference optimizer's flattening of nested AND/OR
 (pinot-core/.../query/optimizer/filter/FlattenAndOrFilterOptimizer.java) is applied.
@@ -292,11 +292,16 @@ class _Parser:
             order_by.append(self._order_item())
             while self.accept("op", ","):
                 order_by.append(self._order_item())
-        limit = 10
+        limit, offset = 10, 0
         if self.accept("kw", "limit"):
             limit = int(self.expect("num")[1])
+            if self.accept("op", ","):  # MySQL's LIMIT m, n: m is the offset
+                offset, limit = limit, int(self.expect("num")[1])
+            elif self.peek()[0] == "ident" and self.peek()[1].lower() == "offset":  # (no keyword: still a column name)
+                self.next()
+                offset = int(self.expect("num")[1])
         self.expect("eof")
-        return table, select, filt, group_by, order_by, limit
+        return table, select, filt, group_by, order_by, limit, offset
 
     def _select_item(self):
         if self.accept("op", "*"):  # SELECT * (expanded per segment: SelectionOperatorUtils.extractExpressions)
@@ -398,7 +403,7 @@ def parse(sql: str) -> QueryContext:
         key = _OPTION_RESOLVER.get(m.group(1).lower(), m.group(1))
         options[key] = v[1:-1].replace("''", "'") if v.startswith("'") else v
         sql = sql[m.end():]
-    table, select, filt, group_by, order_by, limit = _Parser(sql).query()
+    table, select, filt, group_by, order_by, limit, offset = _Parser(sql).query()
     aggs = []
     nh = str(options.get("enableNullHandling", "false")).strip().lower() == "true"
     for e, _ in select:
@@ -423,4 +428,4 @@ def parse(sql: str) -> QueryContext:
         for e, _ in select:
             if isinstance(e, FilterClause) or (isinstance(e, Identifier) and e.name == "*" and len(select) > 1):
                 raise SqlError(f"select expression {e} in a selection query")
-    return QueryContext(table, select, aggs, filt, group_by, resolved_order, limit, options)
+    return QueryContext(table, select, aggs, filt, group_by, resolved_order, limit, options, offset)
