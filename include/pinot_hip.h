@@ -72,6 +72,19 @@
                               * as well. A STRING column: VarByteChunkForwardIndexWriter v1..v3 chunks (per chunk
                               * numDocsPerChunk BE int start offsets, then the UTF-8 bytes), any codec */
 
+#define PHIP_FWD_FIXED_BIT_MV 4 /* a dictionary-encoded multi-value column, FixedBitMVForwardIndexWriter: numChunks BE
+                                * int chunk offsets (docsPerChunk = ceil(2048 / (float)(total_values / num_docs)), the
+                                * inner division an integer one), a bitset of total_values bits with a bit (MSB first) at
+                                * each doc's first value, then the total_values dict ids bit-packed as PHIP_FWD_FIXED_BIT
+                                * packs them. A buffer that starts with 0xffabcdef is the entry-dictionary encoding
+                                * (FixedBitMVEntryDictForwardIndexWriter): PHIP_ERR_UNSUPPORTED. Every doc has at least
+                                * one value: a bitset whose set bits are not one per doc fails the load. Resident as the packed ids plus num_docs + 1 u32 value offsets.
+                                * Filter leaves (PHIP_LEAF_DICT_RANGE / DICT_SET / INVERTED) match a doc when ANY of its
+                                * values matches, an exclusive leaf when NONE of its values is in the set
+                                * (BaseDictionaryBasedPredicateEvaluator.applyMV); an aggregation reads the column only
+                                * through a row reduction (phip_derived_column.reduction). No null vector; not a group-by
+                                * key, a select expression or an operand of arithmetic (PHIP_ERR_UNSUPPORTED). */
+
 typedef struct phip_column_desc {
   const char *name;
   int32_t data_type;      /* PHIP_TYPE_* */
@@ -91,6 +104,9 @@ typedef struct phip_column_desc {
    * dense doc words for PHIP_LEAF_NULL leaves. */
   const uint8_t *null_vector;
   uint64_t null_vector_bytes;
+  int64_t total_values;       /* PHIP_FWD_FIXED_BIT_MV: the values of all docs (totalNumberOfEntries); else unused */
+  int32_t max_values_per_doc; /* PHIP_FWD_FIXED_BIT_MV: the longest row (maxNumberOfMultiValues); else unused */
+  int32_t reserved_mv;
 } phip_column_desc;
 
 typedef struct phip_segment_desc {
@@ -253,10 +269,24 @@ typedef struct phip_expr_op {
   double double_value;
 } phip_expr_op;
 
+/* Row reductions of a multi-value column (PHIP_FWD_FIXED_BIT_MV): a derived column whose program is the single op
+ * PUSH_COLUMN of that column and whose `reduction` is one of the kinds below holds one value per doc -- the doc's
+ * number of values, the sum of its values, or its smallest / largest value -- so COUNTMV / SUMMV / AVGMV / MINMV /
+ * MAXMV / MINMAXRANGEMV are PHIP_AGG_SUM / MIN / MAX over it (mv.hip). LENGTH is int64; SUM is int64 for an INT / LONG
+ * column while max_values_per_doc x the dictionary's extremes stays below 2^62 and the whole sum below 2^58, else the
+ * row's values added left to right in double (SumMVAggregationFunction.aggregate); MIN / MAX are doubles. Cached and
+ * budgeted with the arithmetic columns. A reduction over a single-value column, reduction 0 over a multi-value one, and
+ * any reduction in a library without the kernel are PHIP_ERR_UNSUPPORTED. */
+#define PHIP_MV_REDUCE_NONE 0   /* an arithmetic program (above) */
+#define PHIP_MV_REDUCE_LENGTH 1
+#define PHIP_MV_REDUCE_SUM 2
+#define PHIP_MV_REDUCE_MIN 3
+#define PHIP_MV_REDUCE_MAX 4
+
 typedef struct phip_derived_column {
   const phip_expr_op *ops;
   int32_t num_ops;
-  int32_t reserved;
+  int32_t reduction; /* PHIP_MV_REDUCE_* */
 } phip_derived_column;
 
 typedef struct phip_aggregation {

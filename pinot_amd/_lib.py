@@ -19,7 +19,7 @@ PHIP_ERR_NO_DEVICE = 5
 PHIP_ERR_TIMEOUT = 6
 PHIP_ERR_CANCELLED = 7
 
-FWD_FIXED_BIT, FWD_SORTED, FWD_RAW_CHUNK, FWD_HLL_REGISTERS = 0, 1, 2, 3
+FWD_FIXED_BIT, FWD_SORTED, FWD_RAW_CHUNK, FWD_HLL_REGISTERS, FWD_FIXED_BIT_MV = 0, 1, 2, 3, 4
 NODE_LEAF, NODE_AND, NODE_OR, NODE_NOT = 0, 1, 2, 3
 LEAF_MATCH_ALL, LEAF_MATCH_NONE, LEAF_DICT_RANGE, LEAF_DICT_SET, LEAF_DOC_RANGES, LEAF_INVERTED, LEAF_RAW_RANGE, \
     LEAF_RAW_SET, LEAF_RAW_STRING_RANGE, LEAF_RAW_STRING_SET, LEAF_NULL = range(11)
@@ -37,6 +37,8 @@ EXPR_COLUMN, EXPR_ADD, EXPR_SUB, EXPR_MUL = range(4)
 # phip_expr_op codes and limits of a derived value column's postfix program (include/pinot_hip.h PHIP_EXPR_OP_*)
 EXPR_OP_PUSH_COLUMN, EXPR_OP_PUSH_LONG, EXPR_OP_PUSH_DOUBLE, EXPR_OP_ADD, EXPR_OP_SUB, EXPR_OP_MUL, EXPR_OP_DIV = range(7)
 EXPR_MAX_OPS, EXPR_MAX_STACK, EXPR_MAX_COLUMNS = 32, 8, 8
+# phip_derived_column.reduction: a multi-value column's row reduction (include/pinot_hip.h PHIP_MV_REDUCE_*)
+MV_REDUCE_NONE, MV_REDUCE_LENGTH, MV_REDUCE_SUM, MV_REDUCE_MIN, MV_REDUCE_MAX = range(5)
 
 EXPORTED_SYMBOLS = (
     "phip_init", "phip_shutdown", "phip_device_count", "phip_last_error", "phip_version",
@@ -69,7 +71,9 @@ class ColumnDesc(ctypes.Structure):
                 ("forward", ctypes.c_void_p), ("forward_bytes", ctypes.c_uint64),
                 ("dictionary", ctypes.c_void_p), ("dictionary_bytes", ctypes.c_uint64),
                 ("inverted", ctypes.c_void_p), ("inverted_bytes", ctypes.c_uint64),
-                ("null_vector", ctypes.c_void_p), ("null_vector_bytes", ctypes.c_uint64)]
+                ("null_vector", ctypes.c_void_p), ("null_vector_bytes", ctypes.c_uint64),
+                ("total_values", ctypes.c_int64), ("max_values_per_doc", ctypes.c_int32),
+                ("reserved_mv", ctypes.c_int32)]
 
 
 class SegmentDesc(ctypes.Structure):
@@ -114,7 +118,7 @@ class ExprOp(ctypes.Structure):
 
 
 class DerivedColumn(ctypes.Structure):
-    _fields_ = [("ops", ctypes.POINTER(ExprOp)), ("num_ops", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+    _fields_ = [("ops", ctypes.POINTER(ExprOp)), ("num_ops", ctypes.c_int32), ("reduction", ctypes.c_int32)]
 
 
 class QueryDesc(ctypes.Structure):

@@ -166,6 +166,43 @@ struct DevExpr {
   DevCol cols[kExprMaxCols];
 };
 
+// Multi-value columns (PHIP_FWD_FIXED_BIT_MV; mv.hip). Resident: `words`, the dict ids of all rows bit-packed back to
+// back like a single-value column of total_values elements, and `offsets`, num_docs + 1 u32: doc d's values are
+// elements [offsets[d], offsets[d + 1]).
+// One scan leaf of one (segment, program) entry: mv_scan_kernel writes the leaf's dense doc words (bit d % 64 of u64
+// word d / 64; tile t's 32 words at out + t * tile_words, the inverted leaves' interleaved layout) for tiles
+// [0, num_tiles) -- every word, zeros past num_docs. A doc matches when ANY of its values has an id in [lo, hi) (set ==
+// null) or in the id bitmap `set`; `invert` stores the complement within num_docs (an exclusive leaf: no value in the set).
+struct MvScanTask {
+  const uint32_t *words;
+  const uint32_t *offsets;
+  const uint32_t *set;  // bit id % 32 of word id / 32, set_words words, or null
+  uint64_t *out;
+  int32_t tile_words;
+  int32_t num_docs;
+  int32_t num_tiles;
+  int32_t tile_begin;  // the task's first tile among all tasks' tiles (the grid-stride work list)
+  int32_t bits;
+  int32_t lo, hi;
+  int32_t invert;
+  int32_t set_words;
+  int32_t pad;
+};
+// One row-reduction column (include/pinot_hip.h PHIP_MV_REDUCE_*): out[d] = the reduction of doc d's values, int64
+// (integral) or double.
+struct MvReduceTask {
+  const uint32_t *words;
+  const uint32_t *offsets;
+  const void *dict;
+  void *out;
+  int32_t num_docs;
+  int32_t bits;
+  int32_t type;  // PHIP_TYPE_* of the dictionary
+  int32_t kind;  // PHIP_MV_REDUCE_*
+  int32_t integral;
+  int32_t pad;
+};
+
 // One group-by column's key id source for the tuple packing of key spaces above 2^62 (keys.hip tuple_words_kernel).
 constexpr int kMaxTupleCols = 8;
 constexpr int kMaxTupleWords = 4;

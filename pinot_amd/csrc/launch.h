@@ -161,6 +161,16 @@ hipError_t launch_distinct_finish(const DevDistinctQuery *q, const int64_t *keys
 typedef hipError_t (*ExprLauncher)(const DevExpr *e, int32_t num_docs, bool integral, void *out, hipStream_t s);
 void register_expr_launcher(ExprLauncher f);  // defined in runtime.cpp
 
+// ---- mv.hip (multi-value columns) --------------------------------------------------------------------------------
+// Registered like ExprLauncher (null in the host simulation: an MV scan leaf or an MV row reduction is then
+// PHIP_ERR_UNSUPPORTED). scan: `tasks` in device memory, total_tiles = the sum of their num_tiles, on at most
+// max_blocks workgroups. reduce: the task by value.
+struct MvLaunchers {
+  hipError_t (*scan)(const MvScanTask *tasks, int32_t ntasks, int32_t total_tiles, int max_blocks, hipStream_t s);
+  hipError_t (*reduce)(const MvReduceTask &t, hipStream_t s);
+};
+void register_mv_launchers(const MvLaunchers *l);  // defined in runtime.cpp
+
 // ---- keys.hip ----------------------------------------------------------------------------------------------------
 hipError_t set_str_hash_bits(int bits);
 hipError_t launch_raw_images(const void *raw, int32_t type, int64_t n, uint64_t *out, hipStream_t s);

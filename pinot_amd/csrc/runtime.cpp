@@ -288,6 +288,11 @@ struct ColumnStore {
   int32_t vbits = 0;
   uint64_t *nulls = nullptr;    // null value vector as dense doc words (load_null_vector), or null: no null doc
   int64_t null_count = 0;
+  // PHIP_FWD_FIXED_BIT_MV (load_mv_forward): `words` packs the ids of all rows, total_values elements; doc d's values
+  // are elements [mv_off[d], mv_off[d + 1]). No planes, no doc-order values, no records.
+  uint32_t *mv_off = nullptr;
+  int64_t total_values = 0;
+  int32_t max_values = 0;
   std::vector<uint8_t> host_dict;  // dictionary bytes as given (BE / padded strings)
   std::vector<int32_t> sorted_pairs;  // sorted columns: (start,end) per dict id
   std::map<int, uint32_t *> hll;      // per log2m
@@ -306,6 +311,7 @@ struct ColumnStore {
 static inline bool no_dict(const ColumnStore &c) {
   return c.fwd_kind == PHIP_FWD_RAW_CHUNK || c.fwd_kind == PHIP_FWD_HLL_REGISTERS;
 }
+static inline bool is_mv(const ColumnStore &c) { return c.fwd_kind == PHIP_FWD_FIXED_BIT_MV; }
 
 
 // HBM held by group-by records per device (build_records' budget)
@@ -327,6 +333,8 @@ struct DerivedBuf {
 };
 // expr.hip's launcher (launch.h ExprLauncher): null in a library without the kernel unit (the host simulation)
 static phip::ExprLauncher g_expr_launcher = nullptr;
+// mv.hip's launchers (launch.h MvLaunchers): null in a library without the kernel unit
+static const phip::MvLaunchers *g_mv = nullptr;
 // select_order.hip's launchers (launch.h SelectOrderLaunchers): null in a library without the kernel unit
 static const phip::SelectOrderLaunchers *g_sel_order = nullptr;
 static std::atomic<uint64_t> g_derived_clock{0};  // last-use stamps of the derived columns (least recently used first out)
@@ -762,6 +770,66 @@ static int32_t load_varbyte(const phip_column_desc &c, Segment &seg, ColumnStore
   return PHIP_OK;
 }
 
+// Multi-value forward index (FixedBitMVForwardIndexWriter.java:36-158, all big-endian): numChunks int chunk offsets,
+// a bitset of total_values bits with a bit (MSB first: PinotDataBitSet) at each doc's first value, the total_values
+// packed ids. The ids go to cs.words through the single-value byte-swap path; the num_docs + 1 value offsets are built
+// here on the host from the bitset (as load_null_vector builds its words) and checked against the chunk header. A
+// bitset whose set bits are not one per doc -- an empty row cannot be written -- fails the load.
+static int32_t load_mv_forward(const phip_column_desc &c, ColumnStore &cs, Segment &seg, hipStream_t st) {
+  const int64_t n = seg.num_docs, total = c.total_values;
+  // FixedBitMVEntryDictForwardIndexWriter.MAGIC_MARKER (:55,98; ForwardIndexReaderFactory.java:84 tells the encodings
+  // apart by it): rows stored once in an entry dictionary. A FixedBitMVForwardIndexWriter buffer starts with doc 0's
+  // chunk offset, 0.
+  if (c.forward != nullptr && c.forward_bytes >= 4 && be32(c.forward) == 0xffabcdefu)
+    return fail(PHIP_ERR_UNSUPPORTED, "column %s: multi-value forward index in the FixedBitMVEntryDictForwardIndexWriter "
+                "encoding (entry dictionary)", c.name);
+  if (n <= 0 || total < n || total >= ((int64_t)1 << 31))
+    return fail(PHIP_ERR_INVALID, "column %s: %lld values for %lld docs of a multi-value column", c.name, (long long)total,
+                (long long)n);
+  // docsPerChunk = ceil(2048 / (float)(totalNumValues / numDocs)), the inner division an integer one (:78-79)
+  const float avg = (float)(total / n);
+  const int64_t per_chunk = (int64_t)std::ceil((double)(2048.0f / avg));
+  const int64_t num_chunks = (n + per_chunk - 1) / per_chunk;
+  const uint64_t hdr = (uint64_t)num_chunks * 4, bs = (uint64_t)(total + 7) / 8;
+  const uint64_t need = (uint64_t)ceil_div(total * cs.bits, 8);
+  if (c.forward == nullptr || c.forward_bytes < hdr + bs + need)
+    return fail(PHIP_ERR_INVALID, "column %s: multi-value forward index %llu bytes < %llu", c.name,
+                (unsigned long long)c.forward_bytes, (unsigned long long)(hdr + bs + need));
+  const uint8_t *bitset = c.forward + hdr;
+  std::vector<uint32_t> off;
+  off.reserve((size_t)n + 1);
+  int32_t longest = 0;
+  for (int64_t v = 0; v < total; v++) {
+    if (!((bitset[v >> 3] >> (7 - (v & 7))) & 1)) continue;
+    if ((int64_t)off.size() == n || (off.empty() && v != 0))
+      return fail(PHIP_ERR_INVALID, "column %s: the multi-value row starts are not one per doc", c.name);
+    if (!off.empty()) longest = std::max<int32_t>(longest, (int32_t)(v - off.back()));
+    if ((int64_t)off.size() % per_chunk == 0 && (int64_t)be32(c.forward + 4 * (off.size() / per_chunk)) != v)
+      return fail(PHIP_ERR_INVALID, "column %s: chunk offset %lld disagrees with the row starts", c.name,
+                  (long long)(off.size() / per_chunk));
+    off.push_back((uint32_t)v);
+  }
+  if ((int64_t)off.size() != n)
+    return fail(PHIP_ERR_INVALID, "column %s: %lld multi-value row starts for %lld docs", c.name, (long long)off.size(),
+                (long long)n);
+  longest = std::max<int32_t>(longest, (int32_t)(total - off.back()));
+  off.push_back((uint32_t)total);
+  if (c.max_values_per_doc > 0 && c.max_values_per_doc < longest)
+    return fail(PHIP_ERR_INVALID, "column %s: a row of %d values, maxNumberOfMultiValues %d", c.name, longest,
+                c.max_values_per_doc);
+  HIP_TRY(hipMemcpyAsync(cs.words, c.forward + hdr + bs, need, hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_bswap32(cs.words, ceil_div(need, 4), st));
+  void *p;
+  int32_t rc = dev_alloc(seg, ((size_t)n + 1) * 4 + 16, &p);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(p, off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the host offsets go out of scope)
+  cs.mv_off = (uint32_t *)p;
+  cs.total_values = total;
+  cs.max_values = longest;
+  return PHIP_OK;
+}
+
 static int32_t load_column(const phip_column_desc &c, Segment &seg, hipStream_t st, std::vector<void *> &temps) {
   ColumnStore cs;
   if (!c.name) return fail(PHIP_ERR_INVALID, "column without name");
@@ -773,9 +841,15 @@ static int32_t load_column(const phip_column_desc &c, Segment &seg, hipStream_t 
   const int64_t n = seg.num_docs;
   if (c.data_type < PHIP_TYPE_INT || c.data_type > PHIP_TYPE_STRING)
     return fail(PHIP_ERR_INVALID, "column %s: bad data type %d", c.name, c.data_type);
-  if (c.fwd_kind < PHIP_FWD_FIXED_BIT || c.fwd_kind > PHIP_FWD_HLL_REGISTERS)
+  if (c.fwd_kind < PHIP_FWD_FIXED_BIT || c.fwd_kind > PHIP_FWD_FIXED_BIT_MV)
     return fail(PHIP_ERR_INVALID, "column %s: bad forward kind %d", c.name, c.fwd_kind);
-  const bool dict = c.fwd_kind == PHIP_FWD_FIXED_BIT || c.fwd_kind == PHIP_FWD_SORTED;
+  const bool mv = c.fwd_kind == PHIP_FWD_FIXED_BIT_MV;
+  if (mv && c.null_vector != nullptr && c.null_vector_bytes > 0)
+    return fail(PHIP_ERR_UNSUPPORTED, "column %s: a multi-value column with a null value vector", c.name);
+  if (mv && (c.total_values < n || c.total_values >= ((int64_t)1 << 31)))  // (before anything is sized by it)
+    return fail(PHIP_ERR_INVALID, "column %s: %lld values for %lld docs of a multi-value column", c.name,
+                (long long)c.total_values, (long long)n);
+  const bool dict = c.fwd_kind == PHIP_FWD_FIXED_BIT || c.fwd_kind == PHIP_FWD_SORTED || mv;
   if (c.fwd_kind == PHIP_FWD_HLL_REGISTERS) {
     // a star-tree DISTINCTCOUNTHLL pair: per doc 2^log2m u8 registers, copied as they are
     const int lg = c.bits_per_value;
@@ -811,14 +885,21 @@ static int32_t load_column(const phip_column_desc &c, Segment &seg, hipStream_t 
       cs.dict = p;
     }
     cs.bits = num_bits_per_value(c.cardinality - 1);
-    // padded word array: whole tiles + 4 guard words
-    const int64_t nwords = round_up(std::max<int64_t>(n, 1), kTileDocs) * cs.bits / 32 + 4;
+    // padded word array: whole tiles + 4 guard words (a multi-value column: of its total_values elements)
+    const int64_t nelem = mv ? std::max<int64_t>(c.total_values, 0) : n;
+    const int64_t nwords = round_up(std::max<int64_t>(nelem, 1), kTileDocs) * cs.bits / 32 + 4;
     void *wp;
     int32_t rc = dev_alloc(seg, nwords * 4, &wp);
     if (rc) return rc;
     cs.words = (uint32_t *)wp;
     HIP_TRY(hipMemsetAsync(cs.words, 0, nwords * 4, st));
-    if (c.fwd_kind == PHIP_FWD_FIXED_BIT) {
+    if (mv) {
+      if (c.bits_per_value != cs.bits)
+        return fail(PHIP_ERR_INVALID, "column %s: bits %d != getNumBitsPerValue(card-1) = %d", c.name,
+                    c.bits_per_value, cs.bits);
+      rc = load_mv_forward(c, cs, seg, st);
+      if (rc) return rc;
+    } else if (c.fwd_kind == PHIP_FWD_FIXED_BIT) {
       if (c.bits_per_value != cs.bits)
         return fail(PHIP_ERR_INVALID, "column %s: bits %d != getNumBitsPerValue(card-1) = %d", c.name,
                     c.bits_per_value, cs.bits);
@@ -1997,6 +2078,12 @@ struct Plan {
   // device buffers (plan-owned)
   uint8_t *base = nullptr;  // descriptor blob
   size_t tasks_off = 0, dq_off = 0, kinds_off = 0, rgroups_off = 0, num_rgroups = 0;
+  // MV scan leaves (mv.hip mv_scan_kernel): their tasks in the blob, the tiles they write, the grid cap, and the
+  // values they scan per execution (numEntriesScannedInFilter counts an MV leaf's values, MVScanDocIdIterator)
+  size_t mv_tasks_off = 0, num_mv_tasks = 0;
+  int32_t mv_total_tiles = 0;
+  int mv_max_blocks = 1;
+  int64_t mv_entries = 0;
   void *inv_words = nullptr;
   size_t inv_words_total = 0;
   void *fpart = nullptr, *finals = nullptr, *seg_matched = nullptr, *apart = nullptr, *masks = nullptr;
@@ -2300,6 +2387,7 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
 // derived value columns (include/pinot_hip.h phip_expr_op; expr.hip)
 // ================================================================================================
 void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
+void phip::register_mv_launchers(const MvLaunchers *l) { g_mv = l; }
 void phip::register_select_order_launchers(const SelectOrderLaunchers *l) { g_sel_order = l; }
 // the filter kernels of this library store records (filter.hip registers it; false in a build without the kernel units,
 // whose stand-in launch_filter knows nothing of records)
@@ -2318,6 +2406,10 @@ struct ExprInfo {
 int32_t check_expr_program(const phip_query_desc *q, int k, ExprInfo &info) {
   const phip_derived_column &d = q->derived[k];
   if (d.num_ops <= 0 || !d.ops) return fail(PHIP_ERR_INVALID, "derived column %d: empty program", k);
+  if (d.reduction < PHIP_MV_REDUCE_NONE || d.reduction > PHIP_MV_REDUCE_MAX)
+    return fail(PHIP_ERR_INVALID, "derived column %d: unknown reduction %d", k, d.reduction);
+  if (d.reduction != PHIP_MV_REDUCE_NONE && (d.num_ops != 1 || d.ops[0].op != PHIP_EXPR_OP_PUSH_COLUMN))
+    return fail(PHIP_ERR_INVALID, "derived column %d: a row reduction's program is one PUSH_COLUMN", k);
   if (d.num_ops > PHIP_EXPR_MAX_OPS)
     return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: %d ops, at most %d", k, d.num_ops, PHIP_EXPR_MAX_OPS);
   int depth = 0;
@@ -2417,6 +2509,8 @@ struct DerivedJobs {
     std::string key;
     void *out;
     bool integral;
+    bool mv = false;  // a multi-value row reduction (mv.hip): `task`, and a placeholder in progs
+    MvReduceTask task;
   };
   std::vector<DevExpr> progs;
   std::vector<Job> jobs;
@@ -2437,8 +2531,9 @@ int32_t build_derived(DerivedJobs &dj, hipStream_t st) {
   hipError_t e = hipMalloc(&dev_progs, dj.progs.size() * sizeof(DevExpr));
   if (e == hipSuccess) e = hipMemcpyAsync(dev_progs, dj.progs.data(), dj.progs.size() * sizeof(DevExpr), hipMemcpyHostToDevice, st);
   for (size_t i = 0; i < dj.jobs.size() && e == hipSuccess; i++)
-    e = g_expr_launcher(static_cast<const DevExpr *>(dev_progs) + i, dj.progs[i].num_docs, dj.jobs[i].integral,
-                        dj.jobs[i].out, st);
+    e = dj.jobs[i].mv ? g_mv->reduce(dj.jobs[i].task, st)
+                      : g_expr_launcher(static_cast<const DevExpr *>(dev_progs) + i, dj.progs[i].num_docs,
+                                        dj.jobs[i].integral, dj.jobs[i].out, st);
   const hipError_t e2 = hipStreamSynchronize(st);  // (the host and device copies of the programs are read until here)
   if (dev_progs) (void)hipFree(dev_progs);
   if (e != hipSuccess || e2 != hipSuccess) {
@@ -2462,6 +2557,7 @@ int32_t ensure_derived(Segment &sg, const std::vector<Segment *> &segs, const ph
   DevExpr de;
   memset(&de, 0, sizeof(de));
   std::string key = integral ? "i" : "d";
+  if (d.reduction != PHIP_MV_REDUCE_NONE) key = std::string("mv") + (char)('0' + d.reduction) + key;  // (column, reduction, kind)
   std::vector<int> local;  // the segment's columns, in first-push order
   char buf[64];
   for (int i = 0; i < d.num_ops; i++) {
@@ -2559,7 +2655,22 @@ int32_t ensure_derived(Segment &sg, const std::vector<Segment *> &segs, const ph
   g_derived_bytes[sg.device] += bytes;
   if (sg.num_docs > 0) {
     dj.progs.push_back(de);
-    dj.jobs.push_back({&sg, key, db->p, integral});
+    DerivedJobs::Job job{&sg, key, db->p, integral};
+    if (d.reduction != PHIP_MV_REDUCE_NONE) {
+      const ColumnStore &mc = sg.cols[local[0]];
+      job.mv = true;
+      memset(&job.task, 0, sizeof(job.task));
+      job.task.words = mc.words;
+      job.task.offsets = mc.mv_off;
+      job.task.dict = mc.dict;
+      job.task.out = db->p;
+      job.task.num_docs = sg.num_docs;
+      job.task.bits = mc.bits;
+      job.task.type = mc.type;
+      job.task.kind = d.reduction;
+      job.task.integral = integral ? 1 : 0;
+    }
+    dj.jobs.push_back(job);
   }
   ColumnStore cs;
   cs.name = "derived(" + key + ")";
@@ -2645,8 +2756,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   if (q->num_derived < 0 || (q->num_derived > 0 && !q->derived)) return fail(PHIP_ERR_INVALID, "query: bad derived columns");
   if (q->num_derived > 0) {
     const int nd = q->num_derived;
-    if (!g_expr_launcher)
-      return fail(PHIP_ERR_UNSUPPORTED, "derived value columns: this library was built without the expression kernel");
+    for (int k = 0; k < nd; k++) {
+      if (q->derived[k].reduction == PHIP_MV_REDUCE_NONE && !g_expr_launcher)
+        return fail(PHIP_ERR_UNSUPPORTED, "derived value columns: this library was built without the expression kernel");
+      if (q->derived[k].reduction != PHIP_MV_REDUCE_NONE && !g_mv)
+        return fail(PHIP_ERR_UNSUPPORTED, "multi-value row reductions: this library was built without the multi-value kernels");
+    }
     // a derived index anywhere but column_a of a plain SUM / MIN / MAX / DISTINCTCOUNTHLL is misuse
     for (int k = 0; k < q->num_group_by && q->group_by_columns; k++)
       if (q->group_by_columns[k] >= nreal) return fail(PHIP_ERR_INVALID, "group-by column %d is a derived column", k);
@@ -2668,6 +2783,13 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             return fail(PHIP_ERR_INVALID, "derived column %d: numeric expression over STRING column %s", k, cs.name.c_str());
           if (cs.fwd_kind == PHIP_FWD_HLL_REGISTERS)
             return fail(PHIP_ERR_INVALID, "derived column %d: expression over the HLL register column %s", k, cs.name.c_str());
+          if (is_mv(cs) && q->derived[k].reduction == PHIP_MV_REDUCE_NONE)
+            return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: arithmetic over the multi-value column %s", k, cs.name.c_str());
+          if (!is_mv(cs) && q->derived[k].reduction != PHIP_MV_REDUCE_NONE)
+            return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: a multi-value row reduction over the single-value column %s",
+                        k, cs.name.c_str());
+          if (is_mv(cs) && (cs.mv_off == nullptr || cs.dict == nullptr))
+            return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: multi-value column %s has no values to reduce", k, cs.name.c_str());
         }
     }
     derived_aggs.assign(q->aggregations, q->aggregations + (q->aggregations ? naggs : 0));
@@ -2695,11 +2817,29 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       Use u;
       u.k = k;
       u.integral = ag.function == PHIP_AGG_SUM && info[k].all_long && !info[k].has_div;
+      const int red = q->derived[k].reduction;
+      if (red == PHIP_MV_REDUCE_MIN || red == PHIP_MV_REDUCE_MAX) u.integral = false;  // (MIN and MAX read doubles)
       if (u.integral) {
         long double bound = 0;
         u.lo.resize(nseg);
         u.hi.resize(nseg);
         for (int s = 0; s < nseg && u.integral; s++) {
+          if (red != PHIP_MV_REDUCE_NONE) {
+            // a row's length is in [1, max_values]; its sum within max_values x [vmin, vmax] (the 2^62 rule per value)
+            const ColumnStore &mc = segs[s]->cols[colidx[s][info[k].cols[0]]];
+            const long double mx = (long double)std::max(mc.max_values, 1);
+            if (red == PHIP_MV_REDUCE_LENGTH) {
+              u.lo[s] = 1;
+              u.hi[s] = mx;
+            } else {
+              u.integral = mc.has_range && (mc.type == PHIP_TYPE_INT || mc.type == PHIP_TYPE_LONG);
+              u.lo[s] = std::min<long double>(mx * (long double)mc.vmin, (long double)mc.vmin);
+              u.hi[s] = std::max<long double>(mx * (long double)mc.vmax, (long double)mc.vmax);
+              if (std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) >= (long double)((int64_t)1 << 62)) u.integral = false;
+            }
+            if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segs[s]->num_docs;
+            continue;
+          }
           u.integral = expr_int_interval(q->derived[k], *segs[s], colidx[s], &u.lo[s], &u.hi[s]);
           if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segs[s]->num_docs;
         }
@@ -2740,6 +2880,28 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     q = &qd;
   }
   const int ncols = nreal + (int)derived_inputs.size();
+
+  // A multi-value column is read by filter leaves and, through a row reduction, by aggregations: nothing else.
+  for (int s = 0; s < nseg; s++) {
+    auto mv_col = [&](int c) -> const char * {
+      return c >= 0 && c < nreal && is_mv(segs[s]->cols[colidx[s][c]]) ? segs[s]->cols[colidx[s][c]].name.c_str() : nullptr;
+    };
+    for (int k = 0; k < q->num_group_by && q->group_by_columns; k++)
+      if (const char *nm = mv_col(q->group_by_columns[k]))
+        return fail(PHIP_ERR_UNSUPPORTED, "GROUP BY on the multi-value column %s", nm);
+    for (int k = 0; k < q->num_select && q->select; k++) {
+      const char *nm = mv_col(q->select[k].column_a);
+      if (!nm && q->select[k].expr != PHIP_EXPR_COLUMN) nm = mv_col(q->select[k].column_b);
+      if (nm) return fail(PHIP_ERR_UNSUPPORTED, "selecting or ordering by the multi-value column %s", nm);
+    }
+    for (int a = 0; a < naggs && q->aggregations; a++) {
+      const phip_aggregation &ag = q->aggregations[a];
+      if (ag.function == PHIP_AGG_COUNT) continue;
+      const char *nm = mv_col(ag.column_a);
+      if (!nm && ag.expr != PHIP_EXPR_COLUMN) nm = mv_col(ag.column_b);
+      if (nm) return fail(PHIP_ERR_UNSUPPORTED, "a single-value aggregation over the multi-value column %s", nm);
+    }
+  }
 
   // A group-by whose mixed-radix key space exceeds 2^62 groups by tuple keys (build_tuple_keys): the plan is made for
   // one virtual key column (the first group-by column's slot carries its ids) and execute_plan expands the keys.
@@ -3431,7 +3593,13 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     const phip_filter_node *src;
     int entry;  // (segment, program) entry whose program holds the leaf
     int slot;   // index among that entry's inverted leaves
+    // a range / set leaf over a multi-value column: its doc words come from mv_scan_kernel, not from bitmaps
+    bool mv = false;
+    int32_t mv_lo = 0, mv_hi = 0, mv_invert = 0, mv_set_words = 0;
+    size_t mv_set_off = 0;  // the id bitmap in the blob (mv_set_words > 0)
+    bool mv_stats = false;  // the leaf's program counts in numEntriesScannedInFilter
   };
+  std::vector<bool> entry_has_work;  // per (segment, program) entry
   std::vector<InvLeaf> inv_leaves;
   int num_entries = 0;  // (segment, program) entries, pruned ones included
   int64_t total_work = 0;
@@ -3544,6 +3712,32 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       if (after < 0) return fail(PHIP_ERR_INVALID, "segment %d filter: %s", s, err.c_str());
       if (after != ne) return fail(PHIP_ERR_INVALID, "segment %d filter: trailing nodes", s);
       int32_t rc = PHIP_OK;
+      // A range / set leaf over a multi-value column: evaluated by mv_scan_kernel before the filter launch into dense
+      // doc words in the entry's interleaved inverted region; the device node is an inverted leaf over those words.
+      auto mv_leaf = [&](DevNode &dn, size_t ni, const phip_filter_node &fn, int32_t lo, int32_t hi,
+                         const std::vector<uint32_t> *set) {
+        if (!g_mv) {
+          rc = fail(PHIP_ERR_UNSUPPORTED, "a scan leaf over the multi-value column %s: this library was built without "
+                    "the multi-value kernels", sg.cols[colidx[s][fn.column]].name.c_str());
+          return;
+        }
+        int slot = 0;
+        for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
+        InvLeaf L{ni, s, colidx[s][fn.column], &fn, num_entries, slot};
+        L.mv = true;
+        L.mv_lo = lo;
+        L.mv_hi = hi;
+        L.mv_invert = fn.exclusive ? 1 : 0;
+        if (set) {
+          L.mv_set_words = (int32_t)set->size();
+          L.mv_set_off = blob.add(set->data(), set->size() * 4);
+        }
+        L.mv_stats = q->stats_programs == 0 || ((q->stats_programs >> prog) & 1u);
+        inv_leaves.push_back(L);
+        dn.leaf_kind = PHIP_LEAF_INVERTED;
+        dn.count = 0;
+        dn.bits = 0;
+      };
       // leaf -> device node
       auto make_leaf = [&](const phip_filter_node &fn) -> DevNode {
         DevNode dn;
@@ -3567,6 +3761,13 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             if (no_dict(*cs)) { rc = fail(PHIP_ERR_INVALID, "dict leaf on raw column"); break; }
             dn.lo = std::max(0, fn.lo);
             dn.hi = std::min(cs->card, fn.hi);
+            if (is_mv(*cs)) {  // ANY value in the range (every doc has a value: the whole dictionary matches all)
+              if (dn.hi <= dn.lo) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+              else if (dn.lo == 0 && dn.hi == cs->card) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+              else mv_leaf(dn, ni, fn, dn.lo, dn.hi, nullptr);
+              dn.exclusive = 0;
+              break;
+            }
             if (dn.hi <= dn.lo) dn.leaf_kind = PHIP_LEAF_MATCH_NONE;
             else if (dn.lo == 0 && dn.hi == cs->card) dn.leaf_kind = PHIP_LEAF_MATCH_ALL;
             break;
@@ -3585,6 +3786,16 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             if (rc) break;
             // a contiguous id set (or its complement within the dictionary) is a dict-id range
             const bool contiguous = n_in > 0 && mx - mn + 1 == n_in;
+            if (is_mv(*cs)) {
+              // inclusive: ANY value in the set; exclusive: NO value in it -- the complement of the inclusive doc set,
+              // never "any value outside the set" (so an exclusive set is not rewritten into its complement's range)
+              if (n_in == 0) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+              else if (n_in == cs->card) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+              else if (contiguous) mv_leaf(dn, ni, fn, mn, mx + 1, nullptr);
+              else mv_leaf(dn, ni, fn, 0, 0, &bits);
+              dn.exclusive = 0;
+              break;
+            }
             if (cs->bits <= kBitSliceMaxBits) {  // the matching ids as runs (the bit-sliced conjunction ORs <= 4)
               int nr = 0;
               bool prev = false;
@@ -3787,6 +3998,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     }
     ds.node_end = (int32_t)nodes.size();
     num_entries++;
+    entry_has_work.push_back(hull_lo <= hull_hi);
     if (hull_lo > hull_hi) continue;  // no candidate doc: the segment is pruned (no work)
     ds.tile0 = (int32_t)(hull_lo / kTileDocs);
     ds.num_work = (int32_t)(hull_hi / kTileDocs - ds.tile0 + 1);
@@ -3854,6 +4066,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (rc) return rc;
   }
   std::vector<RoaringGroup> rgroups;
+  std::vector<MvScanTask> mv_tasks;
+  std::vector<size_t> mv_set_offs;
+  int64_t mv_total_tiles = 0, mv_entries = 0;
   for (size_t i = 0; i < inv_leaves.size(); i++) {
     const InvLeaf &L = inv_leaves[i];
     const ColumnStore &cs = segs[L.seg]->cols[L.col];
@@ -3864,6 +4079,29 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     node_inv_stride[L.node] = tile_words;
     node_inv_slot[L.node] = L.slot;
     node_inv_leaves[L.node] = entry_leaves[L.entry];
+    if (L.mv) {
+      if (!entry_has_work[L.entry]) continue;  // (a pruned entry: no tile reads the words)
+      MvScanTask t;
+      memset(&t, 0, sizeof(t));
+      t.words = cs.words;
+      t.offsets = cs.mv_off;
+      t.out = words;
+      t.tile_words = tile_words;
+      t.num_docs = segs[L.seg]->num_docs;
+      t.num_tiles = (int32_t)(inv_word_nw[i] / 32);
+      t.tile_begin = mv_total_tiles;
+      t.bits = cs.bits;
+      t.lo = L.mv_lo;
+      t.hi = L.mv_hi;
+      t.invert = L.mv_invert;
+      t.set_words = L.mv_set_words;
+      mv_total_tiles += t.num_tiles;
+      if (mv_total_tiles > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many multi-value scan tiles in one query");
+      if (L.mv_stats) mv_entries += cs.total_values;
+      mv_tasks.push_back(t);
+      mv_set_offs.push_back(L.mv_set_words > 0 ? L.mv_set_off : SIZE_MAX);
+      continue;
+    }
     const size_t first = tasks.size();
     for (int k = 0; k < L.src->count; k++) {
       int32_t id = L.src->ids[k];
@@ -3903,6 +4141,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   }
   const size_t tasks_off = tasks.empty() ? 0 : blob.add(tasks.data(), tasks.size() * sizeof(RoaringTask));
   const size_t rgroups_off = rgroups.empty() ? 0 : blob.add(rgroups.data(), rgroups.size() * sizeof(RoaringGroup));
+  const size_t mv_tasks_off = mv_tasks.empty() ? 0 : blob.reserve(mv_tasks.size() * sizeof(MvScanTask));
 
   // ---- filter kernel configuration (filter.hip) -------------------------------------------------
   // Per 2048-doc tile, the wave's ring slot receives the fixed-bit words of every scanned filter column
@@ -4529,6 +4768,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   if (rc) return rc;
   uint8_t *base = (uint8_t *)dblob;
   for (auto &f : aux_fix) nodes[f.node].aux = base + f.off;
+  for (size_t i = 0; i < mv_tasks.size(); i++)
+    if (mv_set_offs[i] != SIZE_MAX) mv_tasks[i].set = (const uint32_t *)(base + mv_set_offs[i]);
+  if (!mv_tasks.empty()) memcpy(blob.data.data() + mv_tasks_off, mv_tasks.data(), mv_tasks.size() * sizeof(MvScanTask));
   if (!nodes.empty()) memcpy(blob.data.data() + nodes_off, nodes.data(), nodes.size() * sizeof(DevNode));
   if (!dsegs.empty()) memcpy(blob.data.data() + segs_off, dsegs.data(), sizeof(DevSeg) * dsegs.size());
   const DevSeg *dev_segs = (const DevSeg *)(base + segs_off);
@@ -4860,6 +5102,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   P.tasks_off = tasks_off;
   P.rgroups_off = rgroups_off;
   P.num_rgroups = rgroups.size();
+  P.mv_tasks_off = mv_tasks_off;
+  P.num_mv_tasks = mv_tasks.size();
+  P.mv_total_tiles = (int32_t)mv_total_tiles;
+  P.mv_max_blocks = std::max(1, grid_cus * 8);
+  P.mv_entries = mv_entries;
   P.dq_off = dq_off;
   P.kinds_off = kinds_off;
   P.inv_words = inv_words;
@@ -5028,10 +5275,13 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   }
   P.clean = false;
   if (filter_words) HIP_TRY(hipMemsetAsync(fo, 0, (size_t)filter_nwords * 8, st));
-  if (inv_words_total) {  // (every key of every leaf is written: no clearing pass)
+  if (inv_words_total && P.num_rgroups) {  // (every key of every leaf is written: no clearing pass)
     HIP_TRY(launch_roaring_or((const RoaringTask *)(base + tasks_off), (const RoaringGroup *)(base + P.rgroups_off),
                               (int32_t)P.num_rgroups, st));
   }
+  if (P.num_mv_tasks)  // the MV scan leaves' doc words, beside the inverted leaves' (every word of every leaf written)
+    HIP_TRY(g_mv->scan((const MvScanTask *)(base + P.mv_tasks_off), (int32_t)P.num_mv_tasks, P.mv_total_tiles,
+                       P.mv_max_blocks, st));
   if (group_by && dq.mode == GB_HASH) {
     HIP_TRY(hipMemsetAsync(dq.gb_keys, 0xff, (size_t)dq.num_groups * 8, st));  // kHashEmpty
     HIP_TRY(hipMemsetAsync(dq.hash_overflow, 0, 4, st));
@@ -5620,7 +5870,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   auto local_stats = [&](int64_t st6[6]) {
     const int64_t m = has_filter ? (int64_t)fin[32] : docs_in_work;
     st6[0] = m;  // several programs: summed over them (FilteredAggregationOperator adds its infos' statistics)
-    st6[1] = has_filter ? (int64_t)fin[33] : 0;
+    st6[1] = has_filter ? (int64_t)fin[33] + P.mv_entries : 0;  // (an MV scan leaf: its values, counted at plan time)
     st6[2] = m * num_projected;
     st6[3] = total_docs;
     st6[4] = nseg;

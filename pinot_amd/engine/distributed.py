@@ -22,6 +22,7 @@ from typing import List, Optional
 
 import numpy as np
 
+from ..query.context import sv_twin
 from .results import (AggregationResultsBlock, ExecutionStatistics, GroupByResultsBlock, java_double_key,
                       merge_intermediate)
 
@@ -83,7 +84,7 @@ class _Layout:
         self.nsum = 0
         self.nmax = 0
         for a in aggregations:
-            f = a.function
+            f = sv_twin(a.function)
             if f == "count":
                 self.plan.append(("count", self._s(2)))
             elif f == "sum":
@@ -331,8 +332,8 @@ def _merge_records_columnar(block, dist, group):
     vals = list(block.groups.values())
     n = len(keys)
     # per SUM / AVG: does any rank hold a double (the exact integer column then carries doubles for everyone)
-    any_f = [1 if ag.function in ("sum", "avg") and any(
-        v[a] is not None and not isinstance(v[a][0] if ag.function == "avg" else v[a], (int, np.integer))
+    any_f = [1 if sv_twin(ag.function) in ("sum", "avg") and any(
+        v[a] is not None and not isinstance(v[a][0] if sv_twin(ag.function) == "avg" else v[a], (int, np.integer))
         for v in vals) else 0 for a, ag in enumerate(aggs)]
     flags = _reduce(dist, group, np.array([0 if ok else 1] + any_f, dtype=np.int64), dist.ReduceOp.MAX)
     if flags[0]:
@@ -353,7 +354,7 @@ def _merge_records_columnar(block, dist, group):
     # value columns: (kind, agg, part) with kind I (int64) / F (double bits) / P (presence)
     cols = []
     for a, ag in enumerate(aggs):
-        f = ag.function
+        f = sv_twin(ag.function)
         if f == "count":
             cols.append(("I", a, None))
         elif f == "sum":
@@ -366,7 +367,7 @@ def _merge_records_columnar(block, dist, group):
         cols.append(("P", a, None))
     V = np.zeros((n, len(cols)), dtype=np.int64)
     for j, (kind, a, part) in enumerate(cols):
-        f = aggs[a].function
+        f = sv_twin(aggs[a].function)
         if f in _HLL_FUNCS:
             if kind == "P":
                 V[:, j] = 1
@@ -405,7 +406,7 @@ def _merge_records_columnar(block, dist, group):
     G = len(uniq)
     merged_cols = []
     for j, (kind, a, part) in enumerate(cols):
-        f = aggs[a].function
+        f = sv_twin(aggs[a].function)
         if kind == "P":
             acc = np.zeros(G, dtype=np.int64)
             np.maximum.at(acc, inv, Va[:, j])
@@ -436,7 +437,7 @@ def _merge_records_columnar(block, dist, group):
                 key.append(int(uniq[g, c]))
         row = []
         for a, ag in enumerate(aggs):
-            f = ag.function
+            f = sv_twin(ag.function)
             present = merged_cols[col_of[(True, a, None)]][g]
             if f in _HLL_FUNCS:
                 o, m = hoff[a]

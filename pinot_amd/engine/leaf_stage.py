@@ -29,6 +29,7 @@ from typing import List, Optional
 
 import numpy as np
 
+from ..query.context import sv_twin
 from .results import AggregationResultsBlock, GroupByResultsBlock, SelectionResultsBlock
 
 # DataSchema.ColumnDataType stored types on this path
@@ -77,6 +78,7 @@ def convert(value, stored_type):
 
 def _stored_type(function):
     """getIntermediateResultColumnType of the functions on the path (stored types)."""
+    function = sv_twin(function)
     if function == "count":
         return LONG
     if function in ("sum", "min", "max"):
@@ -85,6 +87,7 @@ def _stored_type(function):
 
 
 def _intermediate(function, v):
+    function = sv_twin(function)
     if function == "count":
         return int(v)
     if function in ("sum", "min", "max"):

@@ -26,8 +26,8 @@ import numpy as np
 
 from .. import _lib
 from ..query import predicate as predeval
-from ..query.context import (UNBOUNDED, AggregationInfo, FilterContext, Function, Identifier, Literal, Predicate,
-                             QueryContext, columns_of)
+from ..query.context import (MV_AGGREGATIONS, REFUSED_MV_AGGREGATIONS, UNBOUNDED, AggregationInfo, FilterClause,
+                             FilterContext, Function, Identifier, Literal, Predicate, QueryContext, columns_of, sv_twin)
 from ..query.sql import parse
 from ..spi import (DEFAULT_GROUPBY_TRIM_THRESHOLD, DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE,
                    DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE, DEFAULT_NUM_GROUPS_LIMIT, MAX_TRIM_THRESHOLD, DataType)
@@ -201,7 +201,9 @@ def compile_predicate(seg: GpuSegment, pred) -> object:
         # dict ids gives the identical doc set. PINOT_AMD_INVERTED=always restores the reference choice.
         ids = (np.arange(ev.start, ev.end, dtype=np.int32) if ev.kind == "range"
                else np.asarray(ev.ids, dtype=np.int32))
-        fwd = (seg.num_docs * m.bits_per_element + 7) // 8
+        # (a multi-value forward index streams the ids of all its rows: priced by its own bytes)
+        nvalues = seg.num_docs if getattr(m, "is_single_value", True) else m.total_number_of_entries
+        fwd = (nvalues * m.bits_per_element + 7) // 8
         inv_ok = os.environ.get("PINOT_AMD_INVERTED", "") == "always"
         if not inv_ok:
             ratio = float(os.environ.get("PINOT_AMD_INVERTED_RATIO", INVERTED_COST_RATIO))  # (measurement override)
@@ -444,6 +446,29 @@ class ExprProgram:
     __str__ = __repr__
 
 
+class MvReduce(ExprProgram):
+    """A row reduction of a multi-value column (include/pinot_hip.h PHIP_MV_REDUCE_*): the derived value column that
+    holds, per doc, the number of the column's values, their sum, or their smallest / largest -- what COUNTMV, SUMMV,
+    AVGMV, MINMV, MAXMV and MINMAXRANGEMV read per matched doc (CountMVAggregationFunction.aggregate adds the row's
+    length, SumMVAggregationFunction.aggregate the row's values, MinMV / MaxMV their extremes). Its program is the one
+    PUSH_COLUMN of the column."""
+
+    def __init__(self, column, reduce):
+        super().__init__(((_lib.EXPR_OP_PUSH_COLUMN, column, 0, 0.0),), Identifier(column))
+        self.reduce = reduce
+
+    def __eq__(self, other):
+        return isinstance(other, MvReduce) and self.ops == other.ops and self.reduce == other.reduce
+
+    def __hash__(self):
+        return hash((self.ops, self.reduce))
+
+    def __repr__(self):
+        return f"MvReduce({self.tree}, {('none', 'length', 'sum', 'min', 'max')[self.reduce]})"
+
+    __str__ = __repr__
+
+
 def _fold_literals(name, a, b):
     """Literal(a) op Literal(b): in Python ints when both are ints, the op is not a division and the result is an
     int64 that the double computation reaches too (so both value kinds of the column read one constant); in double, as
@@ -549,6 +574,33 @@ def plan_aggregations(aggs: Sequence[AggregationInfo], programs: Optional[Sequen
         if f == "count":
             mapping.append(("count", slot((_lib.AGG_COUNT, 0, None, None, 0))))
             continue
+        if f in MV_AGGREGATIONS:
+            # each an existing primitive over a row-reduction column; the mapping carries the single-value twin's name,
+            # whose intermediate it is (COUNTMV: the exact int64 SUM of the rows' lengths, a COUNT's long)
+            arg = _strip_cast(ag.argument)
+            if not isinstance(arg, Identifier):
+                raise UnsupportedOnGpu(f"{f}({ag.argument}): arithmetic over a multi-value column is not on the GPU path; "
+                                       f"a multi-value aggregation takes a column")
+
+            def red(fn, kind):
+                return slot((fn, _lib.EXPR_COLUMN, MvReduce(arg.name, kind), None, 0))
+
+            if f == "countmv":
+                mapping.append(("count", red(_lib.AGG_SUM, _lib.MV_REDUCE_LENGTH)))
+            elif f == "summv":
+                mapping.append(("sum", red(_lib.AGG_SUM, _lib.MV_REDUCE_SUM)))
+            elif f == "minmv":
+                mapping.append(("min", red(_lib.AGG_MIN, _lib.MV_REDUCE_MIN)))
+            elif f == "maxmv":
+                mapping.append(("max", red(_lib.AGG_MAX, _lib.MV_REDUCE_MAX)))
+            elif f == "avgmv":
+                mapping.append(("avg", (red(_lib.AGG_SUM, _lib.MV_REDUCE_SUM), red(_lib.AGG_SUM, _lib.MV_REDUCE_LENGTH))))
+            else:
+                mapping.append(("minmaxrange", (red(_lib.AGG_MIN, _lib.MV_REDUCE_MIN), red(_lib.AGG_MAX, _lib.MV_REDUCE_MAX))))
+            continue
+        if f in REFUSED_MV_AGGREGATIONS:
+            raise UnsupportedOnGpu(f"aggregation {f} is not on the GPU path: of the multi-value functions only COUNTMV, "
+                                   f"SUMMV, MINMV, MAXMV, AVGMV and MINMAXRANGEMV are")
         expr = _gpu_expr(ag.argument)
         if f == "sum":
             mapping.append(("sum", slot((_lib.AGG_SUM,) + expr + (0,))))
@@ -605,6 +657,7 @@ class GpuCombineOperator:
         for e in query.group_by:
             if not isinstance(e, Identifier):
                 raise UnsupportedOnGpu(f"group-by expression {e}")
+        check_multi_value(query, self.segments, segment_filters is not None)
         self.num_programs = len(programs[0]) if programs is not None else 1
         self.stats_programs = 0  # phip_query_desc.stats_programs: 0 = every program's scans count
         self.prims, self.mapping = plan_aggregations(query.aggregations, programs[1] if programs is not None else None)
@@ -760,7 +813,7 @@ class GpuCombineOperator:
             return
         for p in extrema:
             prog = p[2] if isinstance(p[2], ExprProgram) else None
-            arithmetic = p[1] != _lib.EXPR_COLUMN or prog is not None
+            arithmetic = p[1] != _lib.EXPR_COLUMN or (prog is not None and not isinstance(prog, MvReduce))
             if prog is not None:  # (a division whose divisor can be 0: 0 / 0 is NaN, x / 0 an infinity)
                 z = self._zero_divisor(prog.tree)
                 if z is not None:
@@ -830,6 +883,7 @@ class GpuCombineOperator:
                 keep.append(ops)
                 dcols[k].ops = ops
                 dcols[k].num_ops = len(dp.ops)
+                dcols[k].reduction = getattr(dp, "reduce", _lib.MV_REDUCE_NONE)
             keep.append(dcols)
             q.num_derived = len(self.derived)
             q.derived = dcols
@@ -896,6 +950,8 @@ class GpuCombineOperator:
                 continue
             i = _agg_index(q, ob.expression)
             if i is None or (q.aggregations[i].filter is not None and self.num_programs == 1):
+                return none
+            if q.aggregations[i].function in MV_AGGREGATIONS:  # (its count row is a SUM: the broker's reduce orders it)
                 return none
             f, sl = self.mapping[i]
             if f in ("sum", "min", "max", "count"):
@@ -987,7 +1043,8 @@ class GpuCombineOperator:
             pass
 
     # -- NonScanBasedAggregationOperator (AggregationPlanNode.java:107-118, isFitForNonScanBasedPlan :165-190)
-    _NON_SCAN = ("count", "min", "max", "minmaxrange", "distinctcounthll", "distinctcountrawhll", "distinctcount")
+    _NON_SCAN = ("count", "min", "max", "minmaxrange", "distinctcounthll", "distinctcountrawhll", "distinctcount",
+                 "minmv", "maxmv", "minmaxrangemv")  # (AggregationPlanNode.java:52-59: the *MV extremes too)
 
     def _non_scan_fit(self):
         if self.query.group_by or not all(_is_const(t, _TRUE) for t in self.trees):
@@ -1019,11 +1076,11 @@ class GpuCombineOperator:
                     seg_res.append(s.num_docs)
                     continue
                 d = s.dictionary(ag.argument.name)
-                if ag.function == "min":
+                if sv_twin(ag.function) == "min":
                     seg_res.append(float(d.get(0)))
-                elif ag.function == "max":
+                elif sv_twin(ag.function) == "max":
                     seg_res.append(float(d.get(len(d) - 1)))
-                elif ag.function == "minmaxrange":
+                elif sv_twin(ag.function) == "minmaxrange":
                     seg_res.append((float(d.get(0)), float(d.get(len(d) - 1))))
                 elif ag.function == "distinctcount":  # (NonScanBasedAggregationOperator.java:106-113: the dictionary)
                     seg_res.append(_distinct_value_set(np.asarray(d.values)))
@@ -1618,7 +1675,7 @@ def _holder_default(ag, sample):
     """The value GroupByResultHolder.ensureCapacity leaves in a group no doc of the function's filter reached
     (DoubleGroupByResultHolder: the function's default -- 0.0 for SUM, +/-inf for MIN/MAX; count 0; an empty
     HLL). ``sample`` is another group's intermediate of the same function, to keep its type (exact int sums)."""
-    f = ag.function
+    f = sv_twin(ag.function)
     if f == "sum":
         return 0 if isinstance(sample, int) else 0.0
     if f in ("distinctcounthll", "distinctcountrawhll"):
@@ -2216,6 +2273,88 @@ def use_gpu_option(query: QueryContext, default: bool) -> bool:
     return str(v).strip().lower() == "true"
 
 
+_MV_TRANSFORMS = ("valuein", "arraylength")
+
+
+def _function_names(e, out):
+    if isinstance(e, FilterClause):
+        _function_names(e.function, out)
+    elif isinstance(e, Function):
+        out.add(e.name)
+        for a in e.args:
+            _function_names(a, out)
+    elif isinstance(e, FilterContext):
+        if e.predicate is not None:
+            _function_names(e.predicate.lhs, out)
+        for c in e.children:
+            _function_names(c, out)
+
+
+def check_multi_value(query: QueryContext, segments, star_tree=False):
+    """What the GPU path refuses around multi-value columns, each with its reason: the multi-value
+    transform functions; a multi-value column as a group-by key, a selected or ordering column, the argument of a
+    single-value aggregation or an operand of arithmetic; a multi-value aggregation over a single-value column; any
+    multi-value column under enableNullHandling or over a star-tree's documents."""
+    names = set()
+    for e, _ in query.select:
+        _function_names(e, names)
+    for e in list(query.group_by) + [ob.expression for ob in query.order_by] + \
+            [ag.argument for ag in query.aggregations if ag.argument is not None] + \
+            [f for f in [query.filter] + [ag.filter for ag in query.aggregations] if f is not None]:
+        _function_names(e, names)
+    for fn in _MV_TRANSFORMS:
+        if fn in names:
+            raise UnsupportedOnGpu(f"the multi-value transform function {fn.upper()} is not on the GPU path")
+
+    def seg_mv(s, c):  # (from the column metadata: whatever stands for a segment has that)
+        return s.has_column(c) and not getattr(s.column_metadata(c), "is_single_value", True)
+
+    def is_mv(c):
+        return any(seg_mv(s, c) for s in segments)
+
+    for e in query.group_by:
+        for c in columns_of(e):
+            if is_mv(c):
+                raise UnsupportedOnGpu(f"GROUP BY on the multi-value column {c}")
+    if query.is_selection:
+        for e in [x for x, _ in query.select] + [ob.expression for ob in query.order_by]:
+            for c in columns_of(e):
+                if c == "*" and any(seg_mv(s, n) for s in segments for n in s.segment.columns):
+                    raise UnsupportedOnGpu("selecting every column of a table with a multi-value column")
+                if is_mv(c):
+                    raise UnsupportedOnGpu(f"selecting or ordering by the multi-value column {c}")
+    used = set()
+    for ag in query.aggregations:
+        if ag.argument is None:
+            continue
+        arg = _strip_cast(ag.argument)
+        cols = columns_of(ag.argument)
+        if ag.function in MV_AGGREGATIONS or ag.function in REFUSED_MV_AGGREGATIONS:
+            used.update(c for c in cols if is_mv(c))
+            if isinstance(arg, Identifier) and ag.function in MV_AGGREGATIONS:
+                for s in segments:
+                    if s.has_column(arg.name) and not seg_mv(s, arg.name):
+                        raise UnsupportedOnGpu(f"{ag.function} over the single-value column {arg.name}")
+                    if s.has_column(arg.name) and not s.column_metadata(arg.name).has_dictionary:
+                        raise UnsupportedOnGpu(f"{ag.function} over the raw (no-dictionary) multi-value column {arg.name}")
+            continue
+        for c in cols:
+            if is_mv(c):
+                if isinstance(arg, Identifier):
+                    raise UnsupportedOnGpu(f"the single-value aggregation {ag.function} over the multi-value column {c}")
+                raise UnsupportedOnGpu(f"arithmetic over the multi-value column {c} in {ag.function}({ag.argument})")
+    for f in [query.filter] + [ag.filter for ag in query.aggregations]:
+        if f is not None:
+            try:
+                used.update(c for c in f.columns() if is_mv(c))
+            except NotImplementedError:
+                pass  # (a predicate on an expression: refused where the filter is compiled)
+    if used and null_handling_enabled(query):
+        raise UnsupportedOnGpu(f"the multi-value column {sorted(used)[0]} under enableNullHandling")
+    if used and star_tree:
+        raise UnsupportedOnGpu(f"the multi-value column {sorted(used)[0]} over a star-tree's documents")
+
+
 def _query_columns(query: QueryContext):
     cols = set()
     if query.filter is not None:
@@ -2596,6 +2735,7 @@ class GpuInstancePlanMaker:
             else self.num_groups_limit
         if query.offset and not (query.is_selection and query.order_by and query.limit > 0):
             raise UnsupportedOnGpu("OFFSET on a query that is not an ORDER BY selection (the broker's to apply)")
+        check_multi_value(query, segments)
         if null_handling_enabled(query):
             op = _null_handling_operator(query, segments, limit)
             if op is not None:

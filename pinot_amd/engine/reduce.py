@@ -14,7 +14,7 @@ from typing import List
 
 import numpy as np
 
-from ..query.context import FilterClause, Function, Identifier, Literal, QueryContext, aggregation_call
+from ..query.context import FilterClause, Function, Identifier, Literal, QueryContext, aggregation_call, sv_twin
 from ..spi import DEFAULT_HYPERLOGLOG_LOG2M
 from .results import AggregationResultsBlock, ExecutionStatistics, GroupByResultsBlock, merge_intermediate
 
@@ -115,6 +115,7 @@ def final_result(function: str, v, agg=None):
     PERCENTILE (its percentile) and MODE (its reducer) need beyond the function's name."""
     if v is None:
         return None
+    function = sv_twin(function)  # (COUNTMV is LONG like COUNT; the other *MV functions DOUBLE like their twins)
     if function == "percentile":
         return percentile_of_counts(v, agg.percentile)
     if function == "mode":

@@ -18,6 +18,8 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from ..query.context import sv_twin
+
 
 class JavaDoubleKey(float):
     """A FLOAT / DOUBLE group-key value that Python's float equality would merge with another: -0.0 (== 0.0 in
@@ -189,6 +191,7 @@ def merge_intermediate(function: str, a, b):
         return b
     if b is None:
         return a
+    function = sv_twin(function)  # (COUNTMV merges as COUNT, SUMMV as SUM, ...)
     if function == "count":
         return a + b
     if function == "sum":

@@ -38,6 +38,12 @@ class GpuSegment:
             d.data_type = int(m.data_type)
             if getattr(m, "hll_log2m", 0):  # star-tree DISTINCTCOUNTHLL pair: register rows
                 d.fwd_kind = _lib.FWD_HLL_REGISTERS
+            elif not getattr(m, "is_single_value", True):
+                if not m.has_dictionary:
+                    raise _lib.UnsupportedOnGpu(f"raw (no-dictionary) multi-value column {m.name}")
+                d.fwd_kind = _lib.FWD_FIXED_BIT_MV
+                d.total_values = m.total_number_of_entries
+                d.max_values_per_doc = m.max_number_of_multi_values
             elif not m.has_dictionary:
                 d.fwd_kind = _lib.FWD_RAW_CHUNK
             elif m.is_sorted:

@@ -8,6 +8,7 @@ inputs to the hot path, not rebuilt):
   RangePredicate         pinot-common/.../request/context/predicate/RangePredicate.java:38-143
   QueryContext           pinot-core/.../query/request/context/QueryContext.java:74-757
 """
+import re
 from dataclasses import dataclass, field
 from decimal import Decimal
 from typing import List, Optional, Tuple, Union
@@ -139,6 +140,24 @@ class FilterContext:
 SUPPORTED_AGGREGATIONS = ("count", "sum", "min", "max", "avg", "minmaxrange", "distinctcounthll",
                           "distinctcountrawhll", "distinctcount", "percentile", "mode")
 
+# Aggregations over a multi-value column, each with the single-value function whose intermediate result, merge and
+# final result it shares (CountMVAggregationFunction extends CountAggregationFunction, SumMV... extends Sum..., and so
+# on, pinot-core/.../query/aggregation/function/*MVAggregationFunction.java): per matched doc they read a reduction of
+# the doc's row -- its length, its sum, its extremes.
+MV_AGGREGATIONS = {"countmv": "count", "summv": "sum", "minmv": "min", "maxmv": "max", "avgmv": "avg",
+                   "minmaxrangemv": "minmaxrange"}
+# Multi-value aggregations the parser knows by name and the GPU plan maker refuses
+REFUSED_MV_AGGREGATIONS = ("distinctcountmv", "distinctcountbitmapmv", "distinctcounthllmv", "distinctcountrawhllmv",
+                           "distinctcounthllplusmv", "distinctcountrawhllplusmv", "distinctsummv", "distinctavgmv",
+                           "percentilemv", "percentileestmv", "percentilerawestmv", "percentiletdigestmv",
+                           "percentilerawtdigestmv", "percentilekllmv", "percentilerawkllmv")
+
+
+def sv_twin(function: str) -> str:
+    """The single-value function an aggregation merges and finishes as (itself unless it is one of MV_AGGREGATIONS)."""
+    return MV_AGGREGATIONS.get(function, function)
+
+
 MODE_REDUCERS = ("MIN", "MAX", "AVG")  # ModeAggregationFunction.MultiModeReducerType
 
 
@@ -156,8 +175,11 @@ def java_double_string(v: float) -> str:
 def aggregation_function_of(name: str):
     """A SQL function name -> (canonical aggregation function, percentile or None): PERCENTILEnn is PERCENTILE with
     the integer nn in its name (AggregationFunctionFactory: the name's remainder parsed as the percentile)."""
-    if name in SUPPORTED_AGGREGATIONS:
+    if name in SUPPORTED_AGGREGATIONS or name in MV_AGGREGATIONS or name in REFUSED_MV_AGGREGATIONS:
         return name, None
+    m = re.fullmatch(r"(percentile(?:est|tdigest|kll|rawest|rawtdigest|rawkll)?)\d+mv", name)
+    if m:  # PERCENTILEnnMV and its sketches: known, refused by the GPU plan maker
+        return m.group(1) + "mv", None
     if name.startswith("percentile") and name[len("percentile"):].isdigit():
         return "percentile", int(name[len("percentile"):])
     return None, None

@@ -15,8 +15,10 @@ maps), so the C-ABI receives exactly what ``ImmutableSegmentLoader`` would hand 
                  - raw (no-dictionary) fixed-width column: chunk format v2..v5, any ChunkCompressionType
                    (BaseChunkForwardIndexWriter.java:40-160)
                  - raw STRING column: var-byte chunks v2 / v3 (VarByteChunkForwardIndexWriter.java:37-158)
+                 - multi-value dict column: chunk-offset header, start-of-row bitset, bit-packed dict ids of all
+                   rows back to back (FixedBitMVForwardIndexWriter.java:36-158); never sorted
 * inverted index (card+1) BE u32 absolute offsets + portable Roaring bitmaps
-                 (BitmapInvertedIndexWriter.java:35-156)
+                 (BitmapInvertedIndexWriter.java:35-156); a multi-value doc is under every id it holds
 """
 import ctypes
 import os
@@ -101,6 +103,9 @@ class ColumnMetadata:
     has_inverted_index: bool
     string_width: int = 0  # bytes per padded STRING dictionary entry
     hll_log2m: int = 0     # > 0: a star-tree DISTINCTCOUNTHLL pair column -- per doc 2^log2m u8 HLL registers
+    is_single_value: bool = True         # isSingleValues
+    max_number_of_multi_values: int = 0  # maxNumberOfMultiValues: the longest row of a multi-value column
+    total_number_of_entries: int = 0     # totalNumberOfEntries: the values of all rows of a multi-value column
 
 
 @dataclass
@@ -142,6 +147,91 @@ def pack_bits(dict_ids: np.ndarray, bits: int, native: bool = True) -> bytes:
     nbytes = (n * bits + 7) // 8
     assert len(packed) == nbytes
     return packed.tobytes()
+
+
+MV_PREFERRED_VALUES_PER_CHUNK = 2048  # FixedBitMVForwardIndexWriter.PREFERRED_NUM_VALUES_PER_CHUNK
+
+
+def mv_docs_per_chunk(num_docs: int, total_values: int) -> int:
+    """FixedBitMVForwardIndexWriter.java:78-79: ``float averageValuesPerDoc = totalNumValues / numDocs`` is an integer
+    division widened to float, and the quotient 2048 / that is a float too."""
+    avg = np.float32(total_values // num_docs)
+    return int(np.ceil(np.float64(np.float32(MV_PREFERRED_VALUES_PER_CHUNK) / avg)))
+
+
+def mv_forward_bytes(row_ids: Sequence[np.ndarray], bits: int) -> bytes:
+    """FixedBitMVForwardIndexWriter (FixedBitMVForwardIndexWriter.java:36-158), all big-endian: numChunks ints -- the
+    index of the first value of every docsPerChunk-th doc (updateHeader :139-150) --, a bitset of totalNumValues bits
+    with a bit at each doc's first value (PinotDataBitSet.setBit: 0x80 >>> (bit % 8)), then the dict ids of all rows
+    bit-packed back to back (FixedBitIntReaderWriter over totalNumValues elements: pack_bits)."""
+    n = len(row_ids)
+    lengths = np.fromiter((len(r) for r in row_ids), dtype=np.int64, count=n)
+    if n == 0 or (lengths < 1).any():
+        raise ValueError("a multi-value forward index needs at least one doc and one value per doc")
+    total = int(lengths.sum())
+    starts = np.concatenate(([0], np.cumsum(lengths)[:-1]))
+    per_chunk = mv_docs_per_chunk(n, total)
+    header = starts[::per_chunk].astype(">i4").tobytes()
+    bitset = np.zeros((total + 7) // 8, dtype=np.uint8)
+    np.bitwise_or.at(bitset, starts >> 3, (0x80 >> (starts & 7)).astype(np.uint8))
+    flat = np.concatenate([np.asarray(r, dtype=np.int32) for r in row_ids])
+    return header + bitset.tobytes() + pack_bits(flat, bits)
+
+
+# FixedBitMVEntryDictForwardIndexWriter.MAGIC_MARKER (FixedBitMVEntryDictForwardIndexWriter.java:55,98; the reader
+# factory tells the two encodings apart by it, ForwardIndexReaderFactory.java:84). A FixedBitMVForwardIndexWriter buffer
+# starts with doc 0's chunk offset, which is 0.
+MV_ENTRY_DICT_MAGIC = 0xFFABCDEF
+
+
+def read_mv_offsets(buf: bytes, num_docs: int, total_values: int, bits: int) -> np.ndarray:
+    """The num_docs + 1 value offsets of a FixedBitMVForwardIndexWriter buffer, from its bitset alone (no id is
+    decoded). A bitset whose set bits are not one per doc (the first at value 0), or a chunk header that disagrees with
+    it, raises ValueError; the entry-dictionary encoding (FixedBitMVEntryDictForwardIndexWriter) NotImplementedError."""
+    if len(buf) >= 4 and int.from_bytes(buf[:4], "big") == MV_ENTRY_DICT_MAGIC:
+        raise NotImplementedError("multi-value forward index in the FixedBitMVEntryDictForwardIndexWriter encoding "
+                                  "(entry dictionary) is outside the hot path")
+    if num_docs <= 0 or total_values < num_docs:
+        raise ValueError(f"multi-value forward index: {total_values} values for {num_docs} docs")
+    per_chunk = mv_docs_per_chunk(num_docs, total_values)
+    num_chunks = (num_docs + per_chunk - 1) // per_chunk
+    hdr, bs = num_chunks * 4, (total_values + 7) // 8
+    need = hdr + bs + (total_values * bits + 7) // 8
+    if len(buf) < need:
+        raise ValueError(f"multi-value forward index: {len(buf)} bytes, expected {need}")
+    bitset = np.unpackbits(np.frombuffer(buf, dtype=np.uint8, count=bs, offset=hdr))[:total_values]
+    starts = np.nonzero(bitset)[0]
+    if len(starts) != num_docs or starts[0] != 0:
+        raise ValueError(f"multi-value forward index: {len(starts)} row starts for {num_docs} docs")
+    chunk_starts = np.frombuffer(buf, dtype=">i4", count=num_chunks).astype(np.int64)
+    if not np.array_equal(chunk_starts, starts[::per_chunk]):
+        raise ValueError("multi-value forward index: chunk offsets disagree with the row starts")
+    return np.concatenate((starts, [total_values])).astype(np.int64)
+
+
+def read_mv_forward(buf: bytes, num_docs: int, total_values: int, bits: int):
+    """Host-side read of a FixedBitMVForwardIndexWriter buffer: (flat dict ids, num_docs + 1 value offsets); the checks
+    are read_mv_offsets'."""
+    off = read_mv_offsets(buf, num_docs, total_values, bits)
+    per_chunk = mv_docs_per_chunk(num_docs, total_values)
+    hdr, bs = (num_docs + per_chunk - 1) // per_chunk * 4, (total_values + 7) // 8
+    raw = np.frombuffer(buf, dtype=np.uint8, count=(total_values * bits + 7) // 8, offset=hdr + bs)
+    allbits = np.unpackbits(raw)[:total_values * bits].reshape(total_values, bits).astype(np.int64)
+    ids = (allbits << np.arange(bits - 1, -1, -1)).sum(axis=1).astype(np.int32)
+    return ids, off
+
+
+class _MVValues:
+    """The rows of a multi-value column as SegmentCreator holds them: all values back to back plus row offsets."""
+
+    def __init__(self, rows, np_dtype):
+        self.lengths = np.fromiter((len(r) for r in rows), dtype=np.int64, count=len(rows))
+        self.offsets = np.concatenate(([0], np.cumsum(self.lengths))).astype(np.int64)
+        self.flat = (np.concatenate([np.asarray(r, dtype=np_dtype) for r in rows]) if len(rows)
+                     else np.zeros(0, dtype=np_dtype))
+
+    def __len__(self):
+        return len(self.lengths)
 
 
 def _encode_dictionary(sorted_vals, dt: DataType):
@@ -309,11 +399,24 @@ class SegmentCreator:
         self._ids = {}
         self._nulls = {}
 
-    def add_column(self, name: str, data_type: DataType, values, nulls=None, null_value=None):
-        """nulls: optional bool mask of the docs whose value is null. Those docs store the field's default null value
+    def add_column(self, name: str, data_type: DataType, values, nulls=None, null_value=None, multi_value=False):
+        """multi_value: ``values`` is a sequence of per-doc value sequences, each with at least one value (the forward
+        index cannot represent an empty row); the column is dictionary-encoded and takes no null vector.
+        nulls: optional bool mask of the docs whose value is null. Those docs store the field's default null value
         (``null_value``, else FieldSpec's dimension default: Integer.MIN_VALUE, Long.MIN_VALUE, -inf, "null";
         FieldSpec.java:75-81) in every index, and the column gets a null value vector (NullValueVectorCreator: the
         Roaring bitmap of the null doc ids, written only when some doc is null, :83-92)."""
+        if multi_value:
+            if nulls is not None:
+                raise ValueError(f"column {name}: a multi-value column takes no null vector")
+            if name in self.raw:
+                raise ValueError(f"column {name}: raw (no-dictionary) multi-value columns are not written")
+            rows = [list(r) if not isinstance(r, np.ndarray) else r for r in values]
+            if any(len(r) == 0 for r in rows):
+                raise ValueError(f"column {name}: every doc of a multi-value column needs at least one value")
+            self._cols.append((name, data_type, _MVValues(rows, np.str_ if data_type == DataType.STRING
+                                                          else data_type.numpy)))
+            return self
         if data_type == DataType.STRING:
             arr = np.asarray(values, dtype=object if nulls is not None else np.str_)
         else:
@@ -346,6 +449,10 @@ class SegmentCreator:
             raw = {name: vals for name, _, vals in self._cols}
             for i, cfg in enumerate(self.star_tree_configs):
                 dims = list(cfg.dimensions_split_order)
+                for name, vals in raw.items():
+                    if isinstance(vals, _MVValues) and (name in dims or any(
+                            str(p).split("__", 1)[-1] == name for p in cfg.function_column_pairs)):
+                        raise ValueError(f"star-tree over the multi-value column {name}")
                 for d in dims:
                     if d not in self._ids:
                         raise ValueError(f"star-tree dimension {d} must be a dictionary-encoded column")
@@ -354,7 +461,33 @@ class SegmentCreator:
                                                       {name: dt for name, dt, _ in self._cols}))
         return seg
 
+    def _build_mv_column(self, name, dt, vals: _MVValues, n) -> ColumnIndexes:
+        """A dictionary-encoded multi-value column: the dictionary covers every value of every row, the ids stay in
+        row order, the column is never sorted, and the inverted index puts a doc under every id it holds
+        (SegmentColumnarIndexCreator.indexRow's multi-value branch)."""
+        uniq, flat_ids = _sorted_unique(vals.flat, dt)
+        card = len(uniq)
+        dict_bytes, width = _encode_dictionary(uniq, dt)
+        bits = spi.num_bits_per_value(card - 1)
+        rows = [flat_ids[vals.offsets[d]:vals.offsets[d + 1]] for d in range(n)]
+        fwd = mv_forward_bytes(rows, bits)
+        inv = None
+        if name in self.inverted:
+            docs = np.repeat(np.arange(n, dtype=np.int64), vals.lengths)
+            pairs = np.unique(flat_ids.astype(np.int64) * n + docs)  # (id, doc) pairs, each once, id-major
+            pid, pdoc = pairs // n, pairs % n
+            bounds = np.searchsorted(pid, np.arange(card + 1), side="left")
+            bitmaps = [roaring.serialize(pdoc[bounds[d]:bounds[d + 1]], self.run_optimize) for d in range(card)]
+            offs = np.cumsum([(card + 1) * 4] + [len(b) for b in bitmaps])
+            inv = offs.astype(">u4").tobytes() + b"".join(bitmaps)
+        meta = ColumnMetadata(name, dt, n, card, bits, False, True, inv is not None, width, is_single_value=False,
+                              max_number_of_multi_values=int(vals.lengths.max()),
+                              total_number_of_entries=int(vals.lengths.sum()))
+        return ColumnIndexes(meta, fwd, dict_bytes, inv)
+
     def _build_column(self, name, dt, vals, n) -> ColumnIndexes:
+        if isinstance(vals, _MVValues):
+            return self._build_mv_column(name, dt, vals, n)
         if name in self.raw:
             meta = ColumnMetadata(name, dt, n, 0, 0, False, False, False)
             if dt == DataType.STRING:

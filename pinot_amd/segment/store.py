@@ -7,7 +7,7 @@ bytes, exactly as Pinot wrote them). Two directory layouts exist:
 * v1 / v2 (FilePerIndexDirectory, pinot-segment-local/.../segment/store/FilePerIndexDirectory.java:184-199):
   one file per index, named by V1Constants (pinot-segment-spi/.../V1Constants.java:34-45):
   ``<col>.dict``, ``<col>.sv.unsorted.fwd`` (fixed-bit dict ids), ``<col>.sv.sorted.fwd`` (doc ranges),
-  ``<col>.sv.raw.fwd`` (fixed-byte chunks), ``<col>.bitmap.inv`` (Roaring inverted index), ``<col>.bitmap.nullvalue``
+  ``<col>.sv.raw.fwd`` (fixed-byte chunks), ``<col>.mv.fwd`` (multi-value fixed-bit dict ids), ``<col>.bitmap.inv`` (Roaring inverted index), ``<col>.bitmap.nullvalue``
   (the null value vector: one Roaring bitmap, NullValueVectorCreator.java:83-92);
 * v3 (SingleFileIndexDirectory.java:72-73,165-185,225-310): ``v3/columns.psf`` holds every buffer,
   each preceded by the 8-byte magic 0xdeadbeefdeafbead; ``v3/index_map`` records
@@ -16,7 +16,8 @@ bytes, exactly as Pinot wrote them). Two directory layouts exist:
 
 Column metadata comes from ``metadata.properties`` (ColumnMetadataImpl.fromPropertiesConfiguration,
 pinot-segment-spi/.../index/metadata/ColumnMetadataImpl.java:200-260): cardinality, bitsPerElement,
-dataType, isSorted, hasDictionary, lengthOfEachEntry (STRING dictionary entry width). Like the reference,
+dataType, isSorted, hasDictionary, lengthOfEachEntry (STRING dictionary entry width), and for a multi-value column
+isSingleValues = false, maxNumberOfMultiValues, totalNumberOfEntries. Like the reference,
 a segment whose ``segment.padding.character`` is not ``\\0`` is rejected (ColumnMetadataImpl.java:250-253:
 "Only support zero padding"), which covers both padded legacy layouts in the reference's test data.
 """
@@ -25,11 +26,11 @@ import struct
 from typing import Dict
 
 from ..spi import DataType
-from .creator import ColumnIndexes, ColumnMetadata, ImmutableSegment
+from .creator import ColumnIndexes, ColumnMetadata, ImmutableSegment, read_mv_offsets
 
 MAGIC_MARKER = 0xDEADBEEFDEAFBEAD
 _EXT = {"dictionary": ".dict", "sorted": ".sv.sorted.fwd", "unsorted": ".sv.unsorted.fwd", "raw": ".sv.raw.fwd",
-        "inverted": ".bitmap.inv", "nullvalue": ".bitmap.nullvalue"}
+        "mv": ".mv.fwd", "inverted": ".bitmap.inv", "nullvalue": ".bitmap.nullvalue"}
 # v3 index ids (StandardIndexes.java: "dictionary", "forward_index", "inverted_index", "nullvalue_vector")
 _INDEX_ID = {"dictionary": "dictionary", "inverted": "inverted_index", "nullvalue": "nullvalue_vector"}
 _TYPES = {"INT": DataType.INT, "LONG": DataType.LONG, "FLOAT": DataType.FLOAT, "DOUBLE": DataType.DOUBLE,
@@ -126,7 +127,22 @@ def read_segment_dir(path: str) -> ImmutableSegment:
         bits = int(props.get(key + "bitsPerElement", "0"))
         width = int(props.get(key + "lengthOfEachEntry", "0")) if dt == DataType.STRING else 0
         if not _as_bool(props.get(key + "isSingleValues", "true")):
-            raise NotImplementedError(f"multi-value column {col} is outside the hot path")
+            if not has_dict:  # FixedByteChunkMVForwardIndexReader / VarByteChunkMVForwardIndexReader
+                raise NotImplementedError(f"raw (no-dictionary) multi-value column {col} is outside the hot path")
+            total = int(props.get(key + "totalNumberOfEntries", "0"))
+            fwd = buf(col, "mv")
+            if fwd is None:
+                raise ValueError(f"multi-value column {col} has no forward index")
+            read_mv_offsets(fwd, num_docs, total, bits)  # (one row start per doc, else the load fails here; no id read)
+            inv = buf(col, "inverted")
+            meta = ColumnMetadata(col, dt, num_docs, card, bits, False, True, inv is not None, width,
+                                  is_single_value=False,
+                                  max_number_of_multi_values=int(props.get(key + "maxNumberOfMultiValues", "0")),
+                                  total_number_of_entries=total)
+            if buf(col, "nullvalue") is not None:
+                raise NotImplementedError(f"multi-value column {col} with a null value vector is outside the hot path")
+            seg.columns[col] = ColumnIndexes(meta, fwd, buf(col, "dictionary"), inv)
+            continue
         if not has_dict:
             fwd = buf(col, "raw")
             meta = ColumnMetadata(col, dt, num_docs, 0, 0, False, False, False)
@@ -156,10 +172,14 @@ def write_segment_dir(seg: ImmutableSegment, path: str, version: int = 3) -> str
         key = f"column.{col}."
         lines += [key + f"dataType = {m.data_type.name}", key + f"cardinality = {m.cardinality}",
                   key + f"bitsPerElement = {m.bits_per_element}", key + f"isSorted = {str(m.is_sorted).lower()}",
-                  key + f"hasDictionary = {str(m.has_dictionary).lower()}", key + "isSingleValues = true",
+                  key + f"hasDictionary = {str(m.has_dictionary).lower()}", key + f"isSingleValues = {str(m.is_single_value).lower()}",
                   key + f"hasInvertedIndex = {str(m.has_inverted_index).lower()}",
                   key + f"lengthOfEachEntry = {m.string_width}", key + f"totalDocs = {m.total_docs}"]
-        parts = [("raw" if not m.has_dictionary else ("sorted" if m.is_sorted else "unsorted"), ci.forward)]
+        if not m.is_single_value:
+            lines += [key + f"maxNumberOfMultiValues = {m.max_number_of_multi_values}",
+                      key + f"totalNumberOfEntries = {m.total_number_of_entries}"]
+        parts = [("mv" if not m.is_single_value else
+                  "raw" if not m.has_dictionary else ("sorted" if m.is_sorted else "unsorted"), ci.forward)]
         if ci.dictionary is not None:
             parts.append(("dictionary", ci.dictionary))
         if ci.inverted is not None:
