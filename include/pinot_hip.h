@@ -375,6 +375,32 @@ typedef struct phip_query_desc {
   int32_t reserved_select_order;
   const struct phip_select_order_term *select_order;
   int64_t select_keep;
+  /* SELECT DISTINCT (DistinctOperator, pinot-core/.../operator/query/DistinctOperator.java:57-87, with
+   * DistinctExecutorFactory.java:55-148's dictionary-based executors and DistinctCombineOperator's merge): when
+   * select_distinct = 1 the descriptor is a selection's -- select[] holds the DISTINCT columns in select order
+   * (PHIP_EXPR_COLUMN only, at most 8, single-value dictionary columns of any type), select_order / num_select_order
+   * the ORDER BY terms (each one of the columns; may be 0), select_keep the limit (> 0); select_limit is not read -- and
+   * the result is the distinct rows of the matched docs, ordered by the ORDER BY terms and then by the remaining columns
+   * ascending in select order, cut to the first select_keep rows. The reference's choice among rows that tie on the
+   * terms, and of the `limit` rows of a query without ORDER BY, depends on the docs' arrival order; this rule is one
+   * of the answers it may give. Rows come back in final order in phip_result's selection fields (num_rows,
+   * num_select, select_types, select_values; STRING columns as ids of phip_result_select_dictionary).
+   * The device keys every doc by a mixed radix over the columns' query-global ids (a DESC term's digit is card - 1 -
+   * id; the ORDER BY terms are the most significant digits) and keeps the key set in the regime the key space K =
+   * the product of the cardinalities admits (phip_plan_launch_shape, PHIP_SHAPE_DISTINCT_ROWS_REGIME): a bitmap of K
+   * bits in every workgroup's LDS when its words fit PHIP_DISTINCT_LDS_WORDS (as PHIP_AGG_DISTINCT); else a global
+   * bitmap when K / 8 <= PHIP_DISTINCT_ROWS_MAX_BYTES (environment, read at plan creation, default 256 MiB); else,
+   * for K < 2^63, one u64 key per matched doc sorted and made unique, the buffers (keys, sorted, unique, sort scratch,
+   * sized for every doc of the work list) within PHIP_DISTINCT_ROWS_SORT_BYTES (default 4 GiB). Past that budget, or
+   * at K >= 2^63, PHIP_ERR_UNSUPPORTED.
+   * Statistics: numDocsScanned = every matched doc, numEntriesScannedPostFilter = matched x the columns, the filter
+   * statistics the filter launch's. The reference stops as soon as `limit` distinct rows exist when there is no
+   * ORDER BY, so its counts there depend on where it stopped; whenever it cannot stop early (ORDER BY, or fewer
+   * distinct rows than `limit`) the numbers are equal.
+   * PHIP_ERR_UNSUPPORTED besides: a raw (no-dictionary), multi-value or HLL register column, an expression, several
+   * devices (a node plan), a library built without the distinct-rows kernels. All zero = not a distinct query. */
+  int32_t select_distinct;
+  int32_t reserved_select_distinct;
 } phip_query_desc;
 
 typedef struct phip_select_order_term {
@@ -676,7 +702,9 @@ PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *
 #define PHIP_SHAPE_SELECT_CANDIDATES 10 /* selection ORDER BY: the rows the top-K pruning pass left to gather and sort
                                          * (select_keep <= candidates <= matched when matched >= select_keep, else
                                          * = matched; saturates at INT32_MAX) */
-#define PHIP_LAUNCH_SHAPE_VALUES 11
+#define PHIP_SHAPE_DISTINCT_ROWS_REGIME 11 /* SELECT DISTINCT: how the plan keeps its key set -- 0 not a distinct plan, 1
+                                           * a bitmap in every workgroup's LDS, 2 a global bitmap, 3 sorted keys */
+#define PHIP_LAUNCH_SHAPE_VALUES 12
 PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values);
 
 #endif /* PINOT_HIP_H_ */

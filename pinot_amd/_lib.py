@@ -59,7 +59,11 @@ EXCHANGE_HASH = 4
 
 # phip_plan_launch_shape values, in order (include/pinot_hip.h PHIP_SHAPE_*)
 LAUNCH_SHAPE_FIELDS = ("total_work", "filter_blocks", "agg_blocks", "agg_waves", "nbuf", "num_work_segments",
-                       "distinct_blocks", "select_blocks", "fused_lean", "host_final", "select_candidates")
+                       "distinct_blocks", "select_blocks", "fused_lean", "host_final", "select_candidates",
+                       "distinct_rows_regime")
+# phip_plan_launch_shape's distinct_rows_regime (include/pinot_hip.h PHIP_SHAPE_DISTINCT_ROWS_REGIME)
+DISTINCT_ROWS_NONE, DISTINCT_ROWS_LDS, DISTINCT_ROWS_GLOBAL, DISTINCT_ROWS_SORTED = range(4)
+DISTINCT_ROWS_MAX_COLUMNS = 8  # device.h kMaxDistinctRowCols
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 
@@ -138,7 +142,8 @@ class QueryDesc(ctypes.Structure):
                 ("num_derived", ctypes.c_int32), ("reserved_derived", ctypes.c_int32),
                 ("derived", ctypes.POINTER(DerivedColumn)),
                 ("num_select_order", ctypes.c_int32), ("reserved_select_order", ctypes.c_int32),
-                ("select_order", ctypes.POINTER(SelectOrderTerm)), ("select_keep", ctypes.c_int64)]
+                ("select_order", ctypes.POINTER(SelectOrderTerm)), ("select_keep", ctypes.c_int64),
+                ("select_distinct", ctypes.c_int32), ("reserved_select_distinct", ctypes.c_int32)]
 
 
 class Result(ctypes.Structure):

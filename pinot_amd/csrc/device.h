@@ -535,6 +535,46 @@ struct DevDistinctQuery {
   int64_t gb_stride[kMaxGroupBy];   // the dense group-by's mixed radix (DevAggQuery.gb_stride)
 };
 
+// SELECT DISTINCT (distinct_rows.hip): the distinct rows of the matched docs as mixed-radix keys over the columns'
+// query-global ids. Digit j is column col[j]'s id (card[j] - 1 - id for a DESC order-by term); the ORDER BY terms are
+// the most significant digits, first term highest, the remaining select columns follow in select order, so ascending
+// key order is the result's order. The host picks the regime per plan from the key space (distinct_rows_plan).
+constexpr int kMaxDistinctRowCols = 8;
+constexpr int kDistinctRowsChunkWords = 1024;  // bitmap words per pick chunk: 256 threads x 4 words
+enum DistinctRowsRegime : int32_t {
+  DR_NONE = 0,
+  DR_LDS = 1,     // a bit per key; every workgroup ORs into its own LDS copy, non-zero words flushed by one atomic OR
+  DR_GLOBAL = 2,  // a bit per key in one global bitmap, test before set
+  DR_SORTED = 3,  // one u64 key per matched doc at its rank, then sort + unique
+};
+struct DevDistinctRows {
+  const DevSeg *segs;
+  int32_t num_segs;
+  int32_t total_work;
+  const uint32_t *mask;     // [total_work][64] lane-major tile masks of the filter kernel; null = every doc
+  const int64_t *tile_off;  // DR_SORTED: [total_work + 1] exclusive prefix of matched docs per work tile
+  uint32_t *bitmap;         // DR_LDS / DR_GLOBAL: num_words words, bit i of word w = key 32 w + i
+  int64_t key_space;        // the product of the cardinalities
+  int64_t num_words;        // ceil(key_space / 32)
+  int32_t num_cols;
+  int32_t regime;           // DistinctRowsRegime
+  int32_t col[kMaxDistinctRowCols];   // digit j's column (DevSeg.cols index), most significant digit first
+  int32_t card[kMaxDistinctRowCols];  // its query-global cardinality
+  int32_t desc[kMaxDistinctRowCols];  // 1: the digit is card - 1 - id
+  uint64_t stride[kMaxDistinctRowCols];  // the digit's weight: the product of the later digits' cardinalities
+};
+// Key -> row (distinct_rows_decode_kernel), per SELECT column k: its digit's weight, cardinality and direction, and
+// the column's query-global dictionary as 8-byte result slots (INT / LONG int64, FLOAT / DOUBLE double bits; null for
+// STRING: the id itself is the slot).
+struct DistinctRowsDecode {
+  int32_t num_cols;
+  int32_t pad;
+  uint64_t stride[kMaxDistinctRowCols];
+  int32_t card[kMaxDistinctRowCols];
+  int32_t desc[kMaxDistinctRowCols];
+  const uint64_t *values[kMaxDistinctRowCols];
+};
+
 // ORDER BY on group-by columns for the device trim (trim.hip)
 constexpr int kMaxOrderKeys = 8;
 struct KeyOrder {

@@ -171,6 +171,24 @@ struct MvLaunchers {
 };
 void register_mv_launchers(const MvLaunchers *l);  // defined in runtime.cpp
 
+// ---- distinct_rows.hip (SELECT DISTINCT) -------------------------------------------------------------------------
+// Registered like ExprLauncher (null in the host simulation: a distinct query is then PHIP_ERR_UNSUPPORTED).
+// mark: one pass over the matched docs on at most max_blocks workgroups; DR_LDS / DR_GLOBAL set the docs' key bits in
+// q->bitmap (cleared by the caller), DR_SORTED writes the keys to keys[rank] for rank < num_keys. count: set bits per
+// chunk of kDistinctRowsChunkWords bitmap words into chunk_cnt[0 .. nchunks) and 0 into chunk_cnt[nchunks]. emit:
+// chunk_off = the exclusive prefix of chunk_cnt; the keys of rank < keep, ascending, into keys[rank]; both stride
+// over the chunks on at most max_blocks workgroups. decode:
+// out[k * rows + r] = SELECT column k's slot of keys[r].
+struct DistinctRowsLaunchers {
+  hipError_t (*mark)(const DevDistinctRows *q, int regime, int64_t total_work, size_t lds_bytes, int max_blocks,
+                     uint64_t *keys, int64_t num_keys, hipStream_t s);
+  hipError_t (*count)(const uint32_t *bitmap, int64_t num_words, int max_blocks, int64_t *chunk_cnt, hipStream_t s);
+  hipError_t (*emit)(const uint32_t *bitmap, int64_t num_words, int max_blocks, const int64_t *chunk_off, int64_t keep,
+                     uint64_t *keys, hipStream_t s);
+  hipError_t (*decode)(const uint64_t *keys, int64_t rows, const DistinctRowsDecode &d, uint64_t *out, hipStream_t s);
+};
+void register_distinct_rows_launchers(const DistinctRowsLaunchers *l);  // defined in runtime.cpp
+
 // ---- keys.hip ----------------------------------------------------------------------------------------------------
 hipError_t set_str_hash_bits(int bits);
 hipError_t launch_raw_images(const void *raw, int32_t type, int64_t n, uint64_t *out, hipStream_t s);

@@ -337,6 +337,8 @@ static phip::ExprLauncher g_expr_launcher = nullptr;
 static const phip::MvLaunchers *g_mv = nullptr;
 // select_order.hip's launchers (launch.h SelectOrderLaunchers): null in a library without the kernel unit
 static const phip::SelectOrderLaunchers *g_sel_order = nullptr;
+// distinct_rows.hip's launchers (launch.h DistinctRowsLaunchers): null in a library without the kernel unit
+static const phip::DistinctRowsLaunchers *g_distinct_rows = nullptr;
 static std::atomic<uint64_t> g_derived_clock{0};  // last-use stamps of the derived columns (least recently used first out)
 
 struct Segment {
@@ -2133,6 +2135,16 @@ struct Plan {
   int64_t sel_keep = 0;
   int sel_order_cols = 0, sel_rest_cols = 0;  // distinct columns of the term expressions / of the others alone
   int64_t sel_candidates = 0;                 // of the last execution (phip_plan_launch_shape)
+  // SELECT DISTINCT (distinct_rows.hip): the descriptor in the blob, the regime the key space admits, the bitmap and
+  // the pick's chunk counts / ranks (bitmap regimes), the key -> row table and the columns' dictionaries as result slots
+  bool sel_distinct = false;
+  size_t dr_off = 0;
+  DevDistinctRows drq{};
+  DistinctRowsDecode dr_decode{};
+  void *dr_bits = nullptr;
+  size_t dr_bytes = 0, dr_lds_bytes = 0;
+  int64_t *dr_chunk_cnt = nullptr, *dr_chunk_off = nullptr;
+  int64_t dr_chunks = 0;
   // exact DISTINCTCOUNT and value counts (distinct.hip): slot s = the plan's s-th PHIP_AGG_DISTINCT or
   // PHIP_AGG_VALUE_COUNTS aggregation (dist_agg[s]); the
   // descriptor in the blob, the bitmap [dense key space][row words] cleared and filled by every execution
@@ -2389,6 +2401,7 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
 void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
 void phip::register_mv_launchers(const MvLaunchers *l) { g_mv = l; }
 void phip::register_select_order_launchers(const SelectOrderLaunchers *l) { g_sel_order = l; }
+void phip::register_distinct_rows_launchers(const DistinctRowsLaunchers *l) { g_distinct_rows = l; }
 // the filter kernels of this library store records (filter.hip registers it; false in a build without the kernel units,
 // whose stand-in launch_filter knows nothing of records)
 static bool g_filter_records = false;
@@ -3329,7 +3342,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   sq.num_select = nsel;
   sq.limit = std::max<int64_t>(0, q->select_limit);
   // selection ORDER BY (SelectionOrderByOperator): the terms over select[], the primary term's digit bound
-  const int nord = q->num_select_order;
+  // (a distinct query's terms order its keys, below: the top-K machinery of a selection stays out of it)
+  const bool sel_distinct = q->select_distinct != 0;
+  const int nord = sel_distinct ? 0 : q->num_select_order;
   DevSelOrder so;
   memset(&so, 0, sizeof(so));
   std::vector<SelOrderTerm> sel_terms;
@@ -3434,6 +3449,113 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     so.prune = pr && atoi(pr) == 0 ? 0 : 1;
     so.keep = q->select_keep;
     sq.limit = INT64_MAX;  // the ranks are those of all matched docs
+  }
+  // SELECT DISTINCT (DistinctOperator with the dictionary-based executors): the columns' digits, most significant
+  // first -- the ORDER BY terms in their order, then the remaining columns in select order -- and the regime the key
+  // space admits (distinct_rows.hip)
+  DevDistinctRows drq;
+  DistinctRowsDecode drd;
+  memset(&drq, 0, sizeof(drq));
+  memset(&drd, 0, sizeof(drd));
+  std::vector<std::vector<uint64_t>> dr_values(sel_distinct ? nsel : 0);  // per SELECT column: the dictionary as slots
+  if (sel_distinct) {
+    if (!g_distinct_rows) return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: this library has no distinct_rows kernels");
+    if (nsel == 0) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: no columns");
+    if (nsel > kMaxDistinctRowCols)
+      return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: %d columns, at most %d", nsel, kMaxDistinctRowCols);
+    const int nterm = q->num_select_order;
+    if (nterm < 0 || nterm > nsel || (nterm > 0 && !q->select_order))
+      return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: malformed ORDER BY terms");
+    if (q->select_keep <= 0) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: select_keep must be positive");
+    for (int k = 0; k < nsel; k++) {
+      const int c = q->select[k].column_a;
+      if (q->select[k].expr != PHIP_EXPR_COLUMN)
+        return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: expression %d is not a column", k);
+      for (int k2 = 0; k2 < k; k2++)
+        if (q->select[k2].column_a == c) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: column %s twice", q->columns[c]);
+      for (int s = 0; s < nseg; s++) {
+        const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+        if (no_dict(cs)) return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: raw (no-dictionary) column %s", q->columns[c]);
+        if (cs.fwd_kind == PHIP_FWD_FIXED_BIT_MV)
+          return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: multi-value column %s", q->columns[c]);
+      }
+      if (!col_remap[c]) {
+        std::vector<int> ci(nseg);
+        for (int s = 0; s < nseg; s++) ci[s] = colidx[s][c];
+        int32_t rc = build_remap(*dev, segs, ci, q->columns[c], col_remap[c]);
+        if (rc) return rc;
+      }
+    }
+    std::vector<int> order;  // select indexes, most significant digit first
+    std::vector<int> desc(nsel, 0);
+    for (int j = 0; j < nterm; j++) {
+      const int k = q->select_order[j].select_index;
+      if (k < 0 || k >= nsel) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: ORDER BY term %d names no column", j);
+      if (std::find(order.begin(), order.end(), k) != order.end())
+        return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: ORDER BY names column %d twice", k);
+      const Device::Remap &r = *col_remap[q->select[k].column_a];
+      if (r.type == PHIP_TYPE_STRING)  // (padded-byte order is String.compareTo's only below U+E000, as above)
+        for (uint8_t b : r.values)
+          if (b >= 0xEE)
+            return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: ORDER BY STRING column %s holds a character at or above U+E000",
+                        q->columns[q->select[k].column_a]);
+      order.push_back(k);
+      desc[k] = q->select_order[j].descending ? 1 : 0;
+    }
+    for (int k = 0; k < nsel; k++)
+      if (std::find(order.begin(), order.end(), k) == order.end()) order.push_back(k);
+    long double space = 1;
+    for (int k = 0; k < nsel; k++) space *= (long double)std::max(col_remap[q->select[k].column_a]->card, 1);
+    if (space >= 9223372036854775808.0L)
+      return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: a key space of %.3Lg rows, the limit is 2^63", space);
+    uint64_t stride = 1;
+    drq.num_cols = drd.num_cols = nsel;
+    for (int j = nsel - 1; j >= 0; j--) {
+      const int k = order[j];
+      const int32_t card = std::max(col_remap[q->select[k].column_a]->card, 1);
+      drq.col[j] = q->select[k].column_a;
+      drq.card[j] = drd.card[k] = card;
+      drq.desc[j] = drd.desc[k] = desc[k];
+      drq.stride[j] = drd.stride[k] = stride;
+      stride *= (uint64_t)card;
+    }
+    drq.key_space = (int64_t)stride;
+    drq.num_words = (int64_t)((stride + 31) / 32);
+    // the regime: the bitmap's words within the LDS budget (PHIP_AGG_DISTINCT's, with its clamp), else its bytes within
+    // PHIP_DISTINCT_ROWS_MAX_BYTES, else sorted keys (their budget is checked once the work list is known)
+    const char *lw = getenv("PHIP_DISTINCT_LDS_WORDS");
+    const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(lw ? atoll(lw) : kDistinctLdsWords, 12288));
+    const char *mb = getenv("PHIP_DISTINCT_ROWS_MAX_BYTES");
+    const int64_t max_bytes = mb ? atoll(mb) : (int64_t)256 << 20;
+    drq.regime = drq.num_words <= lds_words ? DR_LDS : (drq.num_words <= max_bytes / 4 ? DR_GLOBAL : DR_SORTED);
+    // key -> row: every column's query-global dictionary as 8-byte result slots (STRING: the id is the slot)
+    for (int k = 0; k < nsel; k++) {
+      const Device::Remap &r = *col_remap[q->select[k].column_a];
+      sel_dicts[k] = col_remap[q->select[k].column_a];
+      if (r.type == PHIP_TYPE_STRING) continue;
+      const int w = type_width(r.type);
+      if (r.raw || r.values.size() != (size_t)r.card * w)
+        return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: column %s has no materialised dictionary", q->columns[q->select[k].column_a]);
+      dr_values[k].resize(std::max(r.card, 1), 0);
+      for (int32_t i = 0; i < r.card; i++) {
+        const uint8_t *p = r.values.data() + (size_t)i * w;
+        uint64_t slot = 0;
+        if (r.type == PHIP_TYPE_INT) {
+          int32_t v;
+          memcpy(&v, p, 4);
+          slot = (uint64_t)(int64_t)v;
+        } else if (r.type == PHIP_TYPE_FLOAT) {
+          float f;
+          memcpy(&f, p, 4);
+          const double d = f;
+          memcpy(&slot, &d, 8);
+        } else {
+          memcpy(&slot, p, 8);  // LONG as int64, DOUBLE as its bits
+        }
+        dr_values[k][i] = slot;
+      }
+    }
+    sq.limit = INT64_MAX;  // (DR_SORTED: the ranks are those of all matched docs)
   }
   int num_projected = 0;
   {
@@ -4762,6 +4884,10 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   const size_t sq2_off = nord > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
   const size_t so_off = nord > 0 ? blob.reserve(sizeof(DevSelOrder)) : 0;
   const size_t dstq_off = ndist > 0 ? blob.reserve(sizeof(DevDistinctQuery)) : 0;
+  const size_t dr_off = sel_distinct ? blob.reserve(sizeof(DevDistinctRows)) : 0;
+  std::vector<size_t> dr_values_off(dr_values.size(), 0);
+  for (size_t k = 0; k < dr_values.size(); k++)
+    if (!dr_values[k].empty()) dr_values_off[k] = blob.add(dr_values[k].data(), dr_values[k].size() * 8);
 
   void *dblob;
   int32_t rc = P.alloc(blob.data.size() + 64, &dblob);
@@ -4943,6 +5069,52 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       P.sel_keep = so.keep;
       P.sel_order_cols = sel_order_cols;
       P.sel_rest_cols = sel_rest_cols;
+    }
+    if (sel_distinct) {
+      drq.segs = dev_segs;
+      drq.num_segs = (int32_t)nent;
+      drq.total_work = (int32_t)total_work;
+      drq.mask = sq.mask;
+      drq.tile_off = P.sel_tile_off;
+      if (drq.regime == DR_SORTED) {
+        // one key per matched doc, at most every doc of the work list: keys, sorted, unique and the sort's scratch
+        int64_t n_max = 0;
+        for (const DevSeg &ds : dsegs) n_max += std::min<int64_t>(ds.num_docs, (int64_t)ds.num_work * kTileDocs);
+        const char *sbe = getenv("PHIP_DISTINCT_ROWS_SORT_BYTES");
+        const int64_t sort_budget = sbe ? atoll(sbe) : (int64_t)4 << 30;
+        size_t tb = 0;
+        if (n_max > INT32_MAX)
+          return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: sorted keys over %lld docs, the limit is 2^31 - 1", (long long)n_max);
+        HIP_TRY(launch_sort_unique_u64(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, std::max<int64_t>(n_max, 1), st));
+        const long double need = 3.0L * 8 * (long double)n_max + (long double)tb;
+        if (need > (long double)sort_budget)
+          return fail(PHIP_ERR_UNSUPPORTED,
+                      "SELECT DISTINCT: a key space of %lld rows needs sorted keys, whose buffers for %lld docs (%.0Lf bytes) "
+                      "exceed PHIP_DISTINCT_ROWS_SORT_BYTES %lld",
+                      (long long)drq.key_space, (long long)n_max, need, (long long)sort_budget);
+      } else {
+        P.dr_bytes = (size_t)round_up(drq.num_words * 4, 16);
+        rc = P.alloc(P.dr_bytes, &P.dr_bits);
+        if (rc) return rc;
+        drq.bitmap = (uint32_t *)P.dr_bits;
+        P.dr_chunks = ceil_div(drq.num_words, kDistinctRowsChunkWords);
+        void *cb;
+        rc = P.alloc(((size_t)P.dr_chunks + 1) * 16, &cb);
+        if (rc) return rc;
+        P.dr_chunk_cnt = (int64_t *)cb;
+        P.dr_chunk_off = P.dr_chunk_cnt + P.dr_chunks + 1;
+        P.dr_lds_bytes = drq.regime == DR_LDS ? (size_t)round_up(std::max<int64_t>(drq.num_words, 1) * 4, 16) : 0;
+      }
+      for (int k = 0; k < nsel; k++)
+        drd.values[k] = dr_values[k].empty() ? nullptr : (const uint64_t *)(base + dr_values_off[k]);
+      memcpy(blob.data.data() + dr_off, &drq, sizeof(drq));
+      P.sel_distinct = true;
+      P.dr_off = dr_off;
+      P.drq = drq;
+      P.dr_decode = drd;
+      P.sel_keep = q->select_keep;
+      // the LDS regime flushes once per workgroup: no more workgroups than stay resident; the others spread wider
+      P.dist_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * (drq.regime == DR_LDS ? 4 : 8));
     }
     P.select = true;
     P.nsel = nsel;
@@ -5665,11 +5837,91 @@ static int32_t execute_select_ordered(Plan &P, Workspace &ws, hipStream_t st, Re
   return PHIP_OK;
 }
 
+// SELECT DISTINCT (distinct_rows.hip): after the filter launch, one pass marks the matched docs' keys (`matched` of
+// them: the filter's count, which the execution has already waited for); the ascending distinct keys come out of the
+// bitmap (count / scan / emit) or of the sort, cut to the limit, and are decoded into the rows. Two waits: the number
+// of distinct keys (the row buffers need it), then the rows. mark_ms: the bitmap's clear and the mark kernel.
+static int32_t execute_select_distinct(Plan &P, Workspace &ws, hipStream_t st, ResultImpl &impl, int64_t matched,
+                                       int64_t *num_rows, float *mark_ms) {
+  const DistinctRowsLaunchers &L = *g_distinct_rows;
+  const DevDistinctRows *drq = (const DevDistinctRows *)(P.base + P.dr_off);
+  const int64_t tw = P.total_work;
+  const size_t nsel = (size_t)P.nsel;
+  int32_t rc;
+  *num_rows = 0;
+  impl.sel_values.clear();
+  if (tw <= 0 || matched <= 0) return PHIP_OK;  // (nothing matched: no key, no launch)
+  if ((rc = check_deadline(P, "before the DISTINCT pass"))) return rc;
+  size_t tb = 0;
+  void *tmp;
+  int64_t counts[2] = {0, 0};  // distinct keys; DR_SORTED: the ranked docs as well
+  const uint64_t *dkeys = nullptr;  // the ascending distinct keys on the device (DR_SORTED)
+  if (P.drq.regime == DR_SORTED) {
+    if (matched > INT32_MAX) return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: %lld matched docs to sort", (long long)matched);
+    const DevSelQuery *dsq = (const DevSelQuery *)(P.base + P.sq_off);
+    size_t sb = 0, ub = 0;
+    void *scan_tmp, *kin, *ksorted, *kuniq, *cnt;
+    HIP_TRY(launch_select_scan(nullptr, &sb, nullptr, nullptr, tw + 1, st));
+    HIP_TRY(launch_sort_unique_u64(nullptr, &ub, nullptr, nullptr, nullptr, nullptr, matched, st));
+    const size_t kb = (size_t)matched * 8;
+    if ((rc = ws.get("sel_scan", std::max<size_t>(sb, 16), &scan_tmp)) || (rc = ws.get("dr_keys", kb, &kin)) ||
+        (rc = ws.get("dr_sorted", kb, &ksorted)) || (rc = ws.get("dr_unique", kb, &kuniq)) ||
+        (rc = ws.get("dr_sort_tmp", std::max<size_t>(ub, 16), &tmp)) || (rc = ws.get("dr_count", 16, &cnt)))
+      return rc;
+    HIP_TRY(launch_select_count(dsq, tw, P.sel_max_blocks, P.sel_tile_cnt, st));
+    HIP_TRY(launch_select_scan(scan_tmp, &sb, P.sel_tile_cnt, P.sel_tile_off, tw + 1, st));
+    HIP_TRY(launch_select_bases(dsq, P.sel_base, P.sel_kept, P.sel_total, st));
+    HIP_TRY(hipEventRecord(P.ev[4], st));
+    HIP_TRY(L.mark(drq, DR_SORTED, tw, 0, P.dist_blocks, (uint64_t *)kin, matched, st));
+    HIP_TRY(hipEventRecord(P.ev[2], st));
+    HIP_TRY(launch_sort_unique_u64(tmp, &ub, (uint64_t *)kin, (uint64_t *)ksorted, (uint64_t *)kuniq, (int64_t *)cnt,
+                                   matched, st));
+    HIP_TRY(hipMemcpyAsync(&counts[0], cnt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&counts[1], P.sel_total + 1, 8, hipMemcpyDeviceToHost, st));
+    dkeys = (const uint64_t *)kuniq;
+  } else {
+    HIP_TRY(launch_select_scan(nullptr, &tb, nullptr, nullptr, P.dr_chunks + 1, st));
+    if ((rc = ws.get("sel_scan", std::max<size_t>(tb, 16), &tmp))) return rc;
+    HIP_TRY(hipEventRecord(P.ev[4], st));
+    HIP_TRY(hipMemsetAsync(P.dr_bits, 0, std::max<size_t>(P.dr_bytes, 16), st));  // every execution starts clean
+    HIP_TRY(L.mark(drq, P.drq.regime, tw, P.dr_lds_bytes, P.dist_blocks, nullptr, 0, st));
+    HIP_TRY(hipEventRecord(P.ev[2], st));
+    HIP_TRY(L.count((const uint32_t *)P.dr_bits, P.drq.num_words, P.sel_max_blocks, P.dr_chunk_cnt, st));
+    HIP_TRY(launch_select_scan(tmp, &tb, P.dr_chunk_cnt, P.dr_chunk_off, P.dr_chunks + 1, st));
+    HIP_TRY(hipMemcpyAsync(&counts[0], P.dr_chunk_off + P.dr_chunks, 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipEventElapsedTime(mark_ms, P.ev[4], P.ev[2]));
+  if (P.drq.regime == DR_SORTED && counts[1] != matched)  // (the ranks and the filter's count: the same masks)
+    return fail(PHIP_ERR_HIP, "SELECT DISTINCT: %lld docs ranked, the filter matched %lld", (long long)counts[1],
+                (long long)matched);
+  if (counts[0] < 0 || counts[0] > matched)
+    return fail(PHIP_ERR_HIP, "SELECT DISTINCT: %lld distinct rows of %lld matched docs", (long long)counts[0], (long long)matched);
+  const int64_t rows = std::min(counts[0], P.sel_keep);
+  impl.sel_values.assign((size_t)rows * nsel, 0);
+  if (rows > 0) {
+    void *out;
+    if ((rc = ws.get("sel_out", (size_t)rows * nsel * 8, &out))) return rc;
+    if (P.drq.regime != DR_SORTED) {
+      void *picked;
+      if ((rc = ws.get("dr_picked", (size_t)rows * 8, &picked))) return rc;
+      HIP_TRY(L.emit((const uint32_t *)P.dr_bits, P.drq.num_words, P.sel_max_blocks, P.dr_chunk_off, rows, (uint64_t *)picked,
+                   st));
+      dkeys = (const uint64_t *)picked;
+    }
+    HIP_TRY(L.decode(dkeys, rows, P.dr_decode, (uint64_t *)out, st));
+    HIP_TRY(hipMemcpyAsync(impl.sel_values.data(), out, (size_t)rows * nsel * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  *num_rows = rows;
+  return PHIP_OK;
+}
+
 // Selection (select.hip): after the filter launch, rank the matched docs per work tile, give each entry its rows
 // (first LIMIT in doc order, concatenated in segment order up to LIMIT) and gather the select expressions.
 // Blocks until the rows are in impl.sel_values; kept[e] receives each entry's kept rows (numDocsScanned).
 static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl &impl, std::vector<int64_t> &kept,
-                              int64_t *num_rows, float *gather_ms) {
+                              int64_t *num_rows, float *gather_ms, int64_t matched) {
   const DevSelQuery *dsq = (const DevSelQuery *)(P.base + P.sq_off);
   const int64_t tw = P.total_work;
   const size_t nent = P.dsegs.size();
@@ -5686,6 +5938,7 @@ static int32_t execute_select(Plan &P, Workspace &ws, hipStream_t st, ResultImpl
     rd->width = 1;
     impl.sel_dicts[k] = rd;
   }
+  if (P.sel_distinct) return execute_select_distinct(P, ws, st, impl, matched, num_rows, gather_ms);
   if (P.sel_ordered) return execute_select_ordered(P, ws, st, impl, kept, num_rows, gather_ms);
   if (tw > 0) {
     size_t tb = 0;
@@ -5827,7 +6080,7 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (mode != EXEC_FINISH) {
     const int32_t sh[PHIP_LAUNCH_SHAPE_VALUES] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves,
                                                   P.fq.nbuf, (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks,
-                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0, 0};
+                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0, 0, P.drq.regime};
     memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {
@@ -6242,7 +6495,9 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (P.select) {
     float t_f = 0.f;
     HIP_TRY(hipEventElapsedTime(&t_f, P.ev[1], P.ev[4]));  // the filter launch, before the events are reused
-    if ((rc = execute_select(P, ws, st, *impl, sel_kept, &sel_rows, &sel_ms))) return rc;
+    if ((rc = execute_select(P, ws, st, *impl, sel_kept, &sel_rows, &sel_ms,
+                             has_filter ? (int64_t)fin[32] : docs_in_work)))
+      return rc;
     P.shape[PHIP_SHAPE_SELECT_CANDIDATES] = (int32_t)std::min<int64_t>(P.sel_candidates, INT32_MAX);
     P.sel_filter_ms = t_f;
   }
@@ -6375,6 +6630,12 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
     for (int s = 0; s < nseg; s++) {
       docs += per_seg[s];
       segs_matched += per_seg[s] > 0 ? 1 : 0;
+    }
+    if (P.sel_distinct) {
+      // DistinctOperator scans every matched doc and projects every DISTINCT column of it: the filter's own numbers
+      // (local_stats above: matched, matched x the projected columns, the segments with a matched doc) stay
+      docs = r.num_docs_scanned;
+      segs_matched = r.num_segments_matched;
     }
     r.num_docs_scanned = docs;
     r.num_entries_scanned_post_filter = docs * P.num_projected;

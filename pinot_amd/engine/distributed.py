@@ -749,6 +749,9 @@ def distributed_block(op, dist=None, group=None, fallback_op=None):
     multi = dist.is_initialized() and dist.get_world_size(group) > 1
     if not multi:
         return op.next_block()
+    if getattr(getattr(op, "query", None), "distinct", False):
+        # (every rank refuses alike, before any collective: the ranks' distinct rows have no merge here)
+        raise _lib.UnsupportedOnGpu("SELECT DISTINCT over several devices: the ranks' rows meet at the broker's reduce")
     if not hasattr(op, "execute_partial"):
         return allreduce_block(op.next_block(), dist, group)
     err = None

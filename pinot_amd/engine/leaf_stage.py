@@ -29,6 +29,7 @@ from typing import List, Optional
 
 import numpy as np
 
+from .._lib import UnsupportedOnGpu
 from ..query.context import sv_twin
 from .results import AggregationResultsBlock, GroupByResultsBlock, SelectionResultsBlock
 
@@ -174,6 +175,10 @@ class GpuLeafStageOperator:
 
     def next_block(self) -> TransferableBlock:
         if self._state == 0:
+            if getattr(self.query, "distinct", False):
+                # (the multi-stage planner turns DISTINCT into a group-by of the leaf stage; a DistinctResultsBlock
+                # has no transferable form here)
+                raise UnsupportedOnGpu("SELECT DISTINCT in the multi-stage leaf stage")
             op = self.plan_maker.make_instance_plan(self.query, self.segments)
             try:
                 blk = op.next_block()

@@ -31,8 +31,8 @@ from ..query.context import (MV_AGGREGATIONS, REFUSED_MV_AGGREGATIONS, UNBOUNDED
 from ..query.sql import parse
 from ..spi import (DEFAULT_GROUPBY_TRIM_THRESHOLD, DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE,
                    DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE, DEFAULT_NUM_GROUPS_LIMIT, MAX_TRIM_THRESHOLD, DataType)
-from .results import (AggregationResultsBlock, ExecutionStatistics, GroupByResultsBlock, SelectionResultsBlock,
-                      double_image_counts, java_double_key,
+from .results import (AggregationResultsBlock, DistinctResultsBlock, ExecutionStatistics, GroupByResultsBlock,
+                      SelectionResultsBlock, double_image_counts, java_double_key,
                       merge_intermediate, value_counts)
 from .segment import GpuSegment
 
@@ -1562,6 +1562,150 @@ class GpuSelectionOperator(GpuCombineOperator):
             lib.phip_result_free(res)
 
 
+DISTINCT_LDS_WORDS = 8192                  # default PHIP_DISTINCT_LDS_WORDS (device.h kDistinctLdsWords) ...
+DISTINCT_LDS_WORDS_MAX = 12288             # ... and its clamp: 48 KiB of LDS per workgroup
+DISTINCT_ROWS_MAX_BYTES = 256 << 20        # default PHIP_DISTINCT_ROWS_MAX_BYTES
+
+
+def distinct_rows_plan(cards, order_terms, lds_words=None, max_bytes=None):
+    """The key layout and the regime of a SELECT DISTINCT on the device (runtime.cpp prepare_plan's arithmetic, as a
+    pure function). ``cards``: the query-global cardinality of every DISTINCT column in select order; ``order_terms``:
+    [(select index, descending)] of the ORDER BY. ``lds_words`` / ``max_bytes``: PHIP_DISTINCT_LDS_WORDS /
+    PHIP_DISTINCT_ROWS_MAX_BYTES (None: the environment's value, else the default).
+
+    A row's key is mixed radix over the columns' query-global ids -- a DESC term's digit is card - 1 - id -- with the
+    ORDER BY terms as the most significant digits, first term highest, and the other columns after them in select
+    order: ascending key order is the result's order. Returns a dict: ``digits`` (select indexes, most significant
+    first), ``strides`` and ``desc`` (per select index), ``key_space`` (the product of the cardinalities),
+    ``words`` (bitmap words, ceil(key_space / 32)) and ``regime``: _lib.DISTINCT_ROWS_LDS when the words fit the LDS
+    budget, DISTINCT_ROWS_GLOBAL when the bitmap's bytes fit max_bytes, else DISTINCT_ROWS_SORTED; a key space of
+    2^63 or more raises UnsupportedOnGpu."""
+    if lds_words is None:
+        lds_words = int(os.environ.get("PHIP_DISTINCT_LDS_WORDS", DISTINCT_LDS_WORDS))
+    if max_bytes is None:
+        max_bytes = int(os.environ.get("PHIP_DISTINCT_ROWS_MAX_BYTES", DISTINCT_ROWS_MAX_BYTES))
+    lds_words = max(0, min(int(lds_words), DISTINCT_LDS_WORDS_MAX))
+    n = len(cards)
+    digits = [k for k, _ in order_terms]
+    if len(set(digits)) != len(digits) or any(not 0 <= k < n for k in digits):
+        raise ValueError("ORDER BY terms must name distinct DISTINCT columns")
+    digits += [k for k in range(n) if k not in digits]
+    desc = [False] * n
+    for k, d in order_terms:
+        desc[k] = bool(d)
+    strides = [0] * n
+    space = 1
+    for k in reversed(digits):
+        strides[k] = space
+        space *= max(int(cards[k]), 1)
+    if space >= 2 ** 63:
+        raise UnsupportedOnGpu(f"SELECT DISTINCT: a key space of {space} rows, the limit is 2^63")
+    words = (space + 31) // 32
+    if words <= lds_words:
+        regime = _lib.DISTINCT_ROWS_LDS
+    elif words <= int(max_bytes) // 4:
+        regime = _lib.DISTINCT_ROWS_GLOBAL
+    else:
+        regime = _lib.DISTINCT_ROWS_SORTED
+    return {"digits": digits, "strides": strides, "desc": desc, "key_space": space, "words": words, "regime": regime}
+
+
+class GpuDistinctOperator(GpuSelectionOperator):
+    """DistinctOperator (pinot-core/.../operator/query/DistinctOperator.java:57-87) over every segment, with
+    DistinctCombineOperator's merge (DistinctResultsBlockMerger over MultiColumnDistinctTable). Per segment the
+    reference hands the matched docs' projection to a DistinctExecutor (DistinctExecutorFactory.java:55-148): over
+    dictionary columns DictionaryBasedSingleColumnDistinctExecutor / DictionaryBasedMultiColumnDistinctExecutor keep a
+    set of dict-id tuples -- with ORDER BY the best LIMIT under a comparator over the order-by columns' dictionary ids
+    (sorted dictionaries: id order is value order), without ORDER BY they stop as soon as LIMIT distinct rows exist.
+    Which of the rows that tie on the order-by terms survive, and which LIMIT rows a query without ORDER BY returns,
+    follow the docs' arrival order there. Here the answer is fixed (reduce.distinct_order): rows ordered by the ORDER
+    BY terms, then by the remaining DISTINCT columns ascending in select order, the first LIMIT of the distinct set --
+    one of the reference's possible answers.
+
+    One filter launch, then distinct_rows.hip: every matched doc's row becomes a mixed-radix key over the columns'
+    query-global dictionary ids (distinct_rows_plan); the key set lives in a bitmap (per workgroup in LDS, or global)
+    or, for a key space past the bitmap budget, in sorted keys; the first LIMIT keys in ascending order are decoded
+    into rows on the device. The block's columns are the DISTINCT expressions in select order. Statistics:
+    numDocsScanned = every matched doc, numEntriesScannedPostFilter = matched x the columns (the reference's when it
+    cannot stop early: ORDER BY, or fewer distinct rows than LIMIT). LIMIT 0 returns the schema only, without the
+    library. Refused (UnsupportedOnGpu): a raw (no-dictionary) column, a multi-value column, an expression, more than
+    8 columns, a STRING order-by dictionary holding a character at or above U+E000, enableNullHandling with a null in
+    a DISTINCT column, OFFSET, segments on several devices, a star-tree's documents (the multi-stage leaf stage and
+    the distributed merge refuse the query themselves)."""
+
+    def __init__(self, query: QueryContext, segments: Sequence[GpuSegment], num_groups_limit: int = 0,
+                 segment_filters=None):
+        if not query.distinct:
+            raise ValueError("GpuDistinctOperator takes a SELECT DISTINCT query")
+        if not segments:
+            raise UnsupportedOnGpu("SELECT DISTINCT over no segments")
+        if segment_filters is not None:
+            raise UnsupportedOnGpu("SELECT DISTINCT over a star-tree's documents")
+        if query.offset:
+            raise UnsupportedOnGpu("OFFSET on a query that is not an ORDER BY selection (the broker's to apply)")
+        if len({getattr(s, "device", -1) for s in segments}) > 1:
+            raise UnsupportedOnGpu("SELECT DISTINCT over segments on several devices (a node plan)")
+        self.exprs = []
+        for e, _ in query.select:
+            if e not in self.exprs:
+                self.exprs.append(e)
+        if len(self.exprs) != len(query.select):
+            raise UnsupportedOnGpu("SELECT DISTINCT naming an expression twice")
+        for e in self.exprs:
+            if not isinstance(e, Identifier):
+                raise UnsupportedOnGpu(f"SELECT DISTINCT over the expression {e}: columns only on the GPU path")
+        if len(self.exprs) > _lib.DISTINCT_ROWS_MAX_COLUMNS:
+            raise UnsupportedOnGpu(f"SELECT DISTINCT over more than {_lib.DISTINCT_ROWS_MAX_COLUMNS} columns")
+        nh = null_handling_enabled(query)
+        for e in self.exprs:
+            for s in segments:
+                if not s.has_column(e.name):
+                    raise KeyError(f"segment {s.name} has no column {e.name}")
+                m = s.column_metadata(e.name)
+                if not getattr(m, "is_single_value", True):
+                    raise UnsupportedOnGpu(f"SELECT DISTINCT over the multi-value column {e.name}")
+                if not m.has_dictionary:
+                    raise UnsupportedOnGpu(f"SELECT DISTINCT over the raw (no-dictionary) column {e.name}")
+                if nh and s.has_null_vector(e.name):
+                    raise UnsupportedOnGpu(f"SELECT DISTINCT with enableNullHandling: column {e.name} holds a null in "
+                                           f"segment {s.name}")
+        self.ordered = bool(query.order_by)
+        self.order_terms = []
+        for ob in query.order_by:  # (sql.parse: every term is one of the DISTINCT expressions)
+            if ob.expression not in self.exprs:
+                raise UnsupportedOnGpu(f"SELECT DISTINCT: ORDER BY {ob.expression} is not a DISTINCT column")
+            self._check_order_column(ob.expression.name, segments, first=False)
+            k = self.exprs.index(ob.expression)
+            if k not in [t[0] for t in self.order_terms]:  # (a repeated term orders nothing further)
+                self.order_terms.append((k, not ob.ascending))
+        self.sel = [(_lib.EXPR_COLUMN, e.name, None) for e in self.exprs]
+        GpuCombineOperator.__init__(self, query, segments, num_groups_limit)
+        for _, a, _ in self.sel:
+            if a not in self.columns:
+                self.columns.append(a)
+        self.names = [str(e) for e in self.exprs]
+        self.types = [_STORED[self.segments[0].column_metadata(e.name).data_type] for e in self.exprs]
+
+    def _desc(self, keep):
+        q = GpuSelectionOperator._desc(self, keep)
+        q.select_distinct = 1
+        q.select_keep = int(self.query.limit)
+        q.select_limit = 0
+        if not self.order_terms:
+            q.num_select_order = 0
+        return q
+
+    def next_block(self):
+        if self.query.limit <= 0:  # (DistinctDataTableReducer returns the schema alone: nothing to compute)
+            stats = ExecutionStatistics(0, 0, 0, sum(s.num_docs for s in self.segments), len(self.segments), 0)
+            return DistinctResultsBlock(self.names, list(self.types), [[] for _ in self.names], stats)
+        blk = GpuSelectionOperator.next_block(self)
+        out = DistinctResultsBlock(blk.column_names, blk.column_types, blk.columns, blk.stats)
+        for a in ("device_ms", "filter_kernel_ms", "agg_kernel_ms", "filter_bytes", "agg_bytes", "fused"):
+            setattr(out, a, getattr(blk, a))
+        return out
+
+
 def _stats_mask(keys, stats_filters) -> int:
     """phip_query_desc.stats_programs for programs keyed by ``keys`` (their FILTER clauses, in program order)."""
     if stats_filters is None:
@@ -2736,6 +2880,8 @@ class GpuInstancePlanMaker:
         if query.offset and not (query.is_selection and query.order_by and query.limit > 0):
             raise UnsupportedOnGpu("OFFSET on a query that is not an ORDER BY selection (the broker's to apply)")
         check_multi_value(query, segments)
+        if query.distinct:  # (makeSegmentPlanNode's DistinctPlanNode: no star-tree, its own null rule)
+            return GpuDistinctOperator(query, segments, limit)
         if null_handling_enabled(query):
             op = _null_handling_operator(query, segments, limit)
             if op is not None:

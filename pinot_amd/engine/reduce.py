@@ -188,6 +188,8 @@ def reduce_blocks(query: QueryContext, blocks) -> ResultTable:
     stats = ExecutionStatistics()
     for b in blocks:
         stats.merge(b.stats)
+    if query.distinct:
+        return _reduce_distinct(query, blocks, stats)
     if query.is_selection:
         if query.order_by and query.limit > 0:
             return _reduce_selection_order_by(query, blocks, stats)
@@ -294,6 +296,36 @@ def _reduce_selection_order_by(query: QueryContext, blocks, stats) -> ResultTabl
         rows.sort(key=lambda r: selection_order_value(r[i]), reverse=not ob.ascending)
     rows = rows[query.offset:query.offset + query.limit]
     return ResultTable(names, [[r[i] for i in picks] for r in rows], stats)
+
+
+def distinct_order(query: QueryContext):
+    """The total order of a SELECT DISTINCT's rows as [(select index, descending)], most significant first: the
+    ORDER BY terms, then the remaining DISTINCT expressions ascending in select order. The reference orders by the
+    ORDER BY terms only and keeps whichever of the tying rows arrived first (DistinctTable's priority queue; without
+    ORDER BY the first LIMIT rows met); ordering the ties as well makes the answer deterministic and is one of the
+    answers the reference may give."""
+    exprs = [e for e, _ in query.select]
+    order = [(exprs.index(ob.expression), not ob.ascending) for ob in query.order_by]
+    seen = {k for k, _ in order}
+    return order + [(k, False) for k in range(len(exprs)) if k not in seen]
+
+
+def _reduce_distinct(query: QueryContext, blocks, stats) -> ResultTable:
+    """DistinctDataTableReducer (pinot-core/.../query/reduce/DistinctDataTableReducer.java:55-79): LIMIT 0 returns the
+    schema only; else the union of the servers' distinct rows (values compare as the comparator's keys do: a double by
+    its Double.compare image, so -0.0 and 0.0 are two values and every NaN one), sorted by distinct_order
+    (toResultTable sorts by the ORDER BY) and cut to LIMIT."""
+    names = [_column_name(e, a, query) for e, a in query.select]
+    if query.limit <= 0:
+        return ResultTable(names, [], stats)
+    rows = {}
+    for b in blocks:
+        for r in b.rows:
+            rows.setdefault(tuple(selection_order_value(v) for v in r), r)
+    keyed = list(rows.items())
+    for k, desc in reversed(distinct_order(query)):  # (list.sort is stable, with reverse too)
+        keyed.sort(key=lambda kr: kr[0][k], reverse=desc)
+    return ResultTable(names, [list(r) for _, r in keyed[:query.limit]], stats)
 
 
 def trim_size(query: QueryContext, min_trim=None) -> int:

@@ -3,6 +3,7 @@
   AggregationResultsBlock  pinot-core/.../operator/blocks/results/AggregationResultsBlock.java:54-155
   GroupByResultsBlock      pinot-core/.../operator/blocks/results/GroupByResultsBlock.java:68-106
   SelectionResultsBlock    pinot-core/.../operator/blocks/results/SelectionResultsBlock.java (DataSchema + rows)
+  DistinctResultsBlock     pinot-core/.../operator/blocks/results/DistinctResultsBlock.java (a DistinctTable's schema + rows)
   ExecutionStatistics      pinot-core/.../operator/ExecutionStatistics.java:42-45
 
 Intermediate results follow each function's intermediate type:
@@ -157,6 +158,13 @@ class SelectionResultsBlock:
     def rows(self) -> List[list]:
         cols = [c.tolist() if isinstance(c, np.ndarray) else list(c) for c in self.columns]
         return [list(r) for r in zip(*cols)] if cols else []
+
+
+@dataclass
+class DistinctResultsBlock(SelectionResultsBlock):
+    """Rows of a SELECT DISTINCT (DistinctResultsBlock.java: a DistinctTable's DataSchema + records): the DISTINCT
+    expressions in select order, the rows distinct and already in the query's total order -- the ORDER BY terms, then
+    the remaining columns ascending in select order -- cut to LIMIT. Held column-wise like a selection block."""
 
 
 def value_counts(values, counts):

@@ -21,6 +21,7 @@ class GpuSegment:
         self.segment = segment
         self.name = segment.name
         self.num_docs = segment.num_docs
+        self.device = device  # (-1: the library's default device)
         self._dicts = {}
         self._sorted = {}
         self._inv_offsets = {}

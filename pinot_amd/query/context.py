@@ -274,6 +274,7 @@ class QueryContext:
     limit: int = 10
     options: dict = field(default_factory=dict)
     offset: int = 0
+    distinct: bool = False  # SELECT DISTINCT (QueryContext.isDistinct: the select list is the DISTINCT columns)
 
     @property
     def is_aggregation(self) -> bool:
@@ -285,8 +286,9 @@ class QueryContext:
 
     @property
     def is_selection(self) -> bool:
-        """A selection (row-returning) query: no aggregation, no group-by (QueryContext.isSelectionQuery)."""
-        return not self.aggregations and not self.group_by
+        """A selection (row-returning) query: no aggregation, no group-by, not DISTINCT
+        (QueryContext.isSelectionQuery; QueryContextUtils.isSelectionQuery excludes a distinct query)."""
+        return not self.aggregations and not self.group_by and not self.distinct
 
     def select_expressions(self, segment_columns=None):
         """SelectionOperatorUtils.extractExpressions (pinot-core/.../query/selection/SelectionOperatorUtils.java:

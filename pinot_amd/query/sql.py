@@ -2,7 +2,7 @@
 
 The reference compiles SQL with Calcite (CalciteSqlParser, pinot-common/.../sql/parsers/) into a
 PinotQuery, then QueryContextConverterUtils builds a QueryContext. This is a recursive-descent
-parser for the subset the parity tests and SSB use: SELECT <aggregations / group columns>
+parser for the subset the parity tests and SSB use: SELECT [DISTINCT] <aggregations / group columns>
 FROM t [WHERE <boolean expr>] [GROUP BY ...] [ORDER BY ...] [LIMIT n [OFFSET m] | LIMIT m, n], with predicates
 =, <>, !=, <, <=, >, >=, [NOT] BETWEEN, [NOT] IN, IS [NOT] NULL and NOT/AND/OR, and +, -, *, / and CAST in
 expressions. The reference optimizer's flattening of nested AND/OR
@@ -272,6 +272,13 @@ class _Parser:
     # query ------------------------------------------------------------------------------
     def query(self):
         self.expect("kw", "select")
+        # DISTINCT directly after SELECT is a keyword (SELECT DISTINCT a, b / SELECT DISTINCT(a)); a column of that
+        # name can only be meant when the select item ends right there
+        t = self.peek()
+        self.distinct = (t[0] == "ident" and str(t[1]).lower() == "distinct"
+                         and self.peek(1) not in (("op", ","), ("kw", "from"), ("kw", "as"), ("eof", None)))
+        if self.distinct:
+            self.next()
         select = [self._select_item()]
         while self.accept("op", ","):
             select.append(self._select_item())
@@ -403,7 +410,9 @@ def parse(sql: str) -> QueryContext:
         key = _OPTION_RESOLVER.get(m.group(1).lower(), m.group(1))
         options[key] = v[1:-1].replace("''", "'") if v.startswith("'") else v
         sql = sql[m.end():]
-    table, select, filt, group_by, order_by, limit, offset = _Parser(sql).query()
+    parser = _Parser(sql)
+    table, select, filt, group_by, order_by, limit, offset = parser.query()
+    distinct = parser.distinct
     aggs = []
     nh = str(options.get("enableNullHandling", "false")).strip().lower() == "true"
     for e, _ in select:
@@ -423,9 +432,23 @@ def parse(sql: str) -> QueryContext:
         if not isinstance(e, Function) or not _is_aggregation(e):
             if group_by and e not in group_by:
                 raise SqlError(f"select expression {e} is neither an aggregation nor a group-by expression")
+    if distinct:
+        # SELECT DISTINCT (CalciteSqlParser rewrites it to the DISTINCT function over the select list and validates):
+        # no aggregation, no GROUP BY, no '*', and every ORDER BY expression among the DISTINCT expressions
+        if aggs:
+            raise SqlError("DISTINCT with an aggregation function is not supported")
+        if group_by:
+            raise SqlError("DISTINCT with GROUP BY is not supported")
+        exprs = [e for e, _ in select]
+        for e in exprs:
+            if isinstance(e, Identifier) and e.name == "*":
+                raise SqlError("DISTINCT * is not supported: name the DISTINCT columns")
+        for ob in resolved_order:
+            if ob.expression not in exprs:
+                raise SqlError(f"ORDER-BY columns should be included in the DISTINCT columns: {ob.expression}")
     if not aggs and not group_by:
         # selection (SelectionOnlyOperator): columns and arithmetic over them; SELECT * stays a single '*'
         for e, _ in select:
             if isinstance(e, FilterClause) or (isinstance(e, Identifier) and e.name == "*" and len(select) > 1):
                 raise SqlError(f"select expression {e} in a selection query")
-    return QueryContext(table, select, aggs, filt, group_by, resolved_order, limit, options, offset)
+    return QueryContext(table, select, aggs, filt, group_by, resolved_order, limit, options, offset, distinct)
