@@ -42,6 +42,11 @@ constexpr int kMaxHllRegs = 1 << 12;  // log2m <= 12 on the GPU path
 constexpr int kFilterBlock = 256;
 constexpr int kFilterWaves = kFilterBlock / kWave;
 constexpr int kMaxRing = 8;           // LDS-DMA ring slots per wave
+#ifndef PHIP_FUSED_WAVES
+#define PHIP_FUSED_WAVES 5  // waves per SIMD the fused launches are compiled for: the LDS admits 5 workgroups (20 waves)
+                            // per CU, and 6 left 68 B of spills per lane (sorted Q1.1 -5 %, profiles/r05j_ablib_waves.log).
+                            // Also the workgroups per CU the small fused scan's shape counts on (fused_shape.h).
+#endif
 // the filter kernel's static LDS at most (filter_kernel.h: block partials 64 B, fused aggregation partials 32 B per
 // accumulator, the record mode's per-wave rows of segment counts 224 B, 16 B of alignment: 432 B with four
 // accumulators); the host sizes the LDS-DMA ring around it
@@ -352,7 +357,8 @@ struct DevFilter {
   int32_t num_segs;
   int32_t total_work;
   int32_t stage_stride;  // bytes of one ring slot (max over segments), multiple of 16
-  int32_t nbuf;          // ring slots per wave (2..kMaxRing): nbuf-1 tiles in flight while one is evaluated
+  int32_t nbuf;          // ring slots per wave (1..kMaxRing): nbuf-1 tiles in flight while one is evaluated (one slot:
+                         // a tile's DMA is issued, awaited and evaluated in turn -- the shape of one-tile waves)
   int32_t xcd_walk;      // 1: XCD-sweep tile order; 2: XCD ranges cut into contiguous per-wave ranges (grid multiple
                          // of 8 for both); 0: contiguous range per wave
   int32_t min_dma;       // min over segments of LDS-DMA wave-instructions per tile (vmcnt lower bound)

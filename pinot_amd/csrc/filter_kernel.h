@@ -1403,10 +1403,7 @@ __device__ __forceinline__ void record_store(const DevFilter &q, const uint64_t 
                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-#ifndef PHIP_FUSED_WAVES
-#define PHIP_FUSED_WAVES 5  // waves per SIMD the fused launches are compiled for: the LDS admits 5 workgroups (20 waves)
-                            // per CU, and 6 left 68 B of spills per lane (sorted Q1.1 -5 %, profiles/r05j_ablib_waves.log)
-#endif
+// (PHIP_FUSED_WAVES, the waves per SIMD the fused launches are compiled for: device.h -- the host sizes grids by it)
 // kBsDefer: the lean shape of a fused aggregation (NA > 0) -- every segment's program is the bit-sliced conjunction
 // (eval_conj_bs; conj == 0 and the conj_range doc-range cut included) and every segment defers its projection
 // (fused_defer / fused_flush from HBM). The P-layout conjunction, the per-tile streamed projection, the tile-mask

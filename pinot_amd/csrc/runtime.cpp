@@ -28,6 +28,7 @@
 
 #include "../../include/pinot_hip.h"
 #include "device.h"
+#include "fused_shape.h"
 #include "host_final.h"
 #include "launch.h"
 #include "node.h"
@@ -57,6 +58,13 @@ static int32_t fail(int32_t code, const char *fmt, ...) {
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
+static_assert(kShapeMaxRing == kMaxRing, "fused_shape.h sizes rings as the filter kernel walks them");
+// PHIP_FILTER_NBUF=1..8 (measurement override, beside PHIP_FILTER_BPC): the filter kernel's ring slots per wave, read
+// when a plan is created; 0 = unset (the plan's own rule).
+static int filter_nbuf_override() {
+  const char *e = getenv("PHIP_FILTER_NBUF");
+  return e && atoi(e) >= 1 ? std::min(kMaxRing, atoi(e)) : 0;
+}
 static inline uint32_t be32(const uint8_t *p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
 }
@@ -4488,6 +4496,16 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (rec_min_fields > 1 && 2 * rec_docs < all_docs)
       for (DevSeg &d : dsegs) d.rec = nullptr;
   }
+  // PHIP_GRID_CUS=n (n >= 1; tests): the CU count every tile-walking launch sizes its grid from, so that a small
+  // input runs the walks with few, long-lived waves (many tiles and segment changes per wave, as at production
+  // sizes). Which kernel variant or walk runs keeps following the device's CU count.
+  int grid_cus = dev->num_cus;
+  if (const char *gc = getenv("PHIP_GRID_CUS")) {
+    if (atoi(gc) >= 1) {
+      grid_cus = atoi(gc);
+      P.sel_max_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * 8);  // (8 workgroups per CU, as the XCD walks' floor)
+    }
+  }
   // Fused aggregation (filter.hip fused_tile): every segment on the conjunctive path, aggregation only
   // (no group-by, no HLL), at most 4 slots, a filter to fuse into. Value columns are then streamed with
   // the tile (one more LDS-DMA region) when the expected matches per 128-byte line of the column reach
@@ -4498,6 +4516,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   for (const DevSeg &ds : dsegs) any_filter_prog |= ds.node_end > ds.node_begin;
   int fused_naggs = 0;
   bool any_defer = false;
+  FusedShape small_shape = {-1, 0, 0, 0, 0};  // mode >= 0: the small fused scan's shape (fused_shape.h)
   std::vector<bool> ids_streamed((size_t)nseg * ncols, false);  // (segment, column): fused tiles stream its ids
   {
     // Fusion saves a launch, the mask round trip and the filter columns' re-read, but a streaming filter
@@ -4541,54 +4560,117 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     for (int a = 0; a < naggs; a++) any_value |= dq.aggs[a].acc != ACC_COUNT;
     if (fuse && any_value) {
       fused_naggs = naggs;
-      const char *sv = getenv("PHIP_STREAM_VALUES");  // measurement override: "0" never, "1" always
+      const char *sv_env = getenv("PHIP_STREAM_VALUES");  // measurement override: "0" never, "1" always
       const char *sp = getenv("PHIP_STREAM_PACKED");  // measurement override: "0" = stream ids + dictionary instead
       const double kStreamValueMin = 0.5;
-      for (size_t i = 0; i < dsegs.size(); i++) {
-        DevSeg &ds = dsegs[i];
-        int32_t off = seg_off[i];
-        const int32_t nstage0 = ds.num_stage;
-        for (int a = 0; a < naggs; a++) {
-          const DevAgg &ag = dq.aggs[a];
-          if (ag.acc == ACC_COUNT) continue;
-          for (int c : {ag.col_a, ag.expr != PHIP_EXPR_COLUMN ? ag.col_b : -1}) {
-            if (c < 0) continue;
-            DevCol &dc = ds.cols[c];
-            if (dc.lds_off >= 0) continue;
-            // a column read through its doc-order values (as_raw) streams its packed ids instead when the tiles are
-            // dense enough: fewer bytes per tile than the values, and no per-doc load at all
-            const int sidx = ds.seg_index % nseg;
-            const ColumnStore &cs = segs[sidx]->cols[colidx[sidx][c]];
-            const bool via_vals = !dc.has_dict && !no_dict(cs);
-            if (!dc.has_dict && !via_vals) continue;
-            // packed values stream as they are (vbits per doc, no dictionary gather after): fused_i64_u / fused_f64_u
-            const bool via_packed = via_vals && dc.vpack != nullptr && !(sp && atoi(sp) == 0);
-            const int32_t bits = via_packed ? dc.vbits : via_vals ? cs.bits : dc.bits;
-            const bool dense = seg_est[i] * (1024.0 / std::max(1, bits)) >= kStreamValueMin;
-            if (!(sv ? atoi(sv) != 0 : (dense && !big))) continue;
-            const int32_t bytes = 256 * bits;
-            // (DevSeg.stage holds kMaxStage sources; the fused kernel's cursor takes up to kMaxConj + kMaxAggStage)
-            if (ds.num_stage >= std::min(kMaxStage, kMaxConj + kMaxAggStage) || off + bytes + 2 * kStagePad > kSlotBudget)
-              continue;
-            if (via_vals && !via_packed) {
-              dc.has_dict = 1;
-              dc.raw = cs.raw;
-              dc.vpack = nullptr;
-              dc.vbits = 0;
-              ids_streamed[(size_t)sidx * ncols + c] = true;
+      // One pass over the segments under a streaming rule (sv: the override's form, null = the density rule): which
+      // value columns join the tile's ring slot, and the slot that results. It writes the segments it is given, so the
+      // small-scan rule below can lay out both of a plan's modes and keep one.
+      struct FusedLayout {
+        std::vector<DevSeg> segs;
+        std::vector<bool> ids;
+        int32_t stride = 0;
+        bool any_defer = false, any_streamed = false;
+      };
+      auto lay_out = [&](const char *sv) {
+        FusedLayout L;
+        L.segs = dsegs;
+        L.ids = ids_streamed;
+        L.stride = stage_stride;
+        for (size_t i = 0; i < L.segs.size(); i++) {
+          DevSeg &ds = L.segs[i];
+          int32_t off = seg_off[i];
+          const int32_t nstage0 = ds.num_stage;
+          for (int a = 0; a < naggs; a++) {
+            const DevAgg &ag = dq.aggs[a];
+            if (ag.acc == ACC_COUNT) continue;
+            for (int c : {ag.col_a, ag.expr != PHIP_EXPR_COLUMN ? ag.col_b : -1}) {
+              if (c < 0) continue;
+              DevCol &dc = ds.cols[c];
+              if (dc.lds_off >= 0) continue;
+              // a column read through its doc-order values (as_raw) streams its packed ids instead when the tiles are
+              // dense enough: fewer bytes per tile than the values, and no per-doc load at all
+              const int sidx = ds.seg_index % nseg;
+              const ColumnStore &cs = segs[sidx]->cols[colidx[sidx][c]];
+              const bool via_vals = !dc.has_dict && !no_dict(cs);
+              if (!dc.has_dict && !via_vals) continue;
+              // packed values stream as they are (vbits per doc, no dictionary gather after): fused_i64_u / fused_f64_u
+              const bool via_packed = via_vals && dc.vpack != nullptr && !(sp && atoi(sp) == 0);
+              const int32_t bits = via_packed ? dc.vbits : via_vals ? cs.bits : dc.bits;
+              const bool dense = seg_est[i] * (1024.0 / std::max(1, bits)) >= kStreamValueMin;
+              if (!(sv ? atoi(sv) != 0 : (dense && !big))) continue;
+              const int32_t bytes = 256 * bits;
+              // (DevSeg.stage holds kMaxStage sources; the fused kernel's cursor takes up to kMaxConj + kMaxAggStage)
+              if (ds.num_stage >= std::min(kMaxStage, kMaxConj + kMaxAggStage) || off + bytes + 2 * kStagePad > kSlotBudget)
+                continue;
+              if (via_vals && !via_packed) {
+                dc.has_dict = 1;
+                dc.raw = cs.raw;
+                dc.vpack = nullptr;
+                dc.vbits = 0;
+                L.ids[(size_t)sidx * ncols + c] = true;
+              }
+              dc.lds_off = off + kStagePad;
+              ds.stage[ds.num_stage++] = {(const uint8_t *)(via_packed ? dc.vpack : dc.words), bytes, dc.lds_off};
+              ds.num_dma += (int32_t)ceil_div(bytes, 1024);
+              off += bytes + 2 * kStagePad;
             }
-            dc.lds_off = off + kStagePad;
-            ds.stage[ds.num_stage++] = {(const uint8_t *)(via_packed ? dc.vpack : dc.words), bytes, dc.lds_off};
-            ds.num_dma += (int32_t)ceil_div(bytes, 1024);
-            off += bytes + 2 * kStagePad;
           }
+          L.stride = std::max(L.stride, off);
+          L.any_streamed |= ds.num_stage != nstage0;
+          // nothing streamed with the tile: the matched docs collect across tiles (filter.hip fused_defer)
+          ds.fused_defer = ds.num_stage == nstage0 ? 1 : 0;
+          if (const char *fd = getenv("PHIP_FUSED_DEFER")) ds.fused_defer = ds.fused_defer && atoi(fd) != 0;  // A/B
+          L.any_defer |= ds.fused_defer != 0;
         }
-        stage_stride = std::max(stage_stride, off);
-        // nothing streamed with the tile: the matched docs collect across tiles (filter.hip fused_defer)
-        ds.fused_defer = ds.num_stage == nstage0 ? 1 : 0;
-        if (const char *fd = getenv("PHIP_FUSED_DEFER")) ds.fused_defer = ds.fused_defer && atoi(fd) != 0;  // A/B
-        any_defer |= ds.fused_defer != 0;
+        return L;
+      };
+      FusedLayout lay = lay_out(sv_env);
+      // A small fused scan (at most 8 tiles per wave at one workgroup per CU: sorted SSB Q1.2's ~3.8K tiles) takes the
+      // shape that gives its waves the fewest tiles each with every workgroup resident at once (fused_shape.h): the
+      // scan is then one generation of waves, and a wave's chain of tiles -- each one's LDS reads, scalar loads and
+      // gathers with nothing else on its SIMD to hide them -- is as short as the LDS allows. Streaming the value
+      // columns makes the ring slot several times the deferred one (Q1.2: LO_EXTENDEDPRICE's packed values beside
+      // the planes), which keeps one workgroup per CU and so several tiles per wave; where the deferred layout spreads
+      // wider it is taken instead, whatever the density rule said. PHIP_FUSED_SMALL=0 keeps the width rule below and
+      // the density rule's mode; PHIP_STREAM_VALUES leaves the rule the one mode it names; PHIP_FILTER_BPC switches
+      // the rule off as it always did. ("small fused scans".)
+      // The rule sizes the XCD range walk, which every fused launch takes; a plan that PHIP_FILTER_WALK forces onto
+      // another walk keeps the older rule below (one workgroup per CU), the shape its tests pin.
+      const char *fs = getenv("PHIP_FUSED_SMALL");
+      const char *fw = getenv("PHIP_FILTER_WALK");
+      if (!getenv("PHIP_FILTER_BPC") && !(fs && atoi(fs) == 0) && (!fw || !strcmp(fw, "xcdc")) && total_work > 0 &&
+          total_work <= (int64_t)dev->num_cus * kFilterWaves * 8) {
+        auto ring_of = [](const FusedLayout &l) {
+          return kFilterWaves * (l.any_defer ? 4 * kFusedRingDefer : 2 * kFusedRingTile);
+        };
+        FusedShapeIn in;
+        memset(&in, 0, sizeof(in));
+        in.tiles = total_work;
+        in.slot[0] = (int32_t)round_up(std::max(lay.stride, 16), 16);
+        in.doc_ring[0] = ring_of(lay);
+        FusedLayout alt;
+        if (!sv_env && lay.any_streamed) {  // the other mode: nothing streamed
+          alt = lay_out("0");
+          in.slot[1] = (int32_t)round_up(std::max(alt.stride, 16), 16);
+          in.doc_ring[1] = ring_of(alt);
+        }
+        in.static_lds = kFilterStaticLds;
+        in.waves = kFilterWaves;
+        in.cus = grid_cus;
+        in.wave_cap = PHIP_FUSED_WAVES;
+        in.force_nbuf = filter_nbuf_override();
+        small_shape = fused_small_shape(in);
+        if (getenv("PHIP_SHAPE_TRACE"))  // measurement aid: the rule's inputs and choice, once per plan
+          fprintf(stderr, "phip_shape: tiles %lld slot %d/%d doc_ring %d/%d cus %d cap %d force %d -> mode %d blocks %d nbuf %d bpc %d T %lld\n",
+                  (long long)in.tiles, in.slot[0], in.slot[1], in.doc_ring[0], in.doc_ring[1], in.cus, in.wave_cap, in.force_nbuf,
+                  small_shape.mode, small_shape.blocks, small_shape.nbuf, small_shape.bpc, (long long)small_shape.T);
+        if (small_shape.mode == 1) lay = std::move(alt);
       }
+      dsegs = std::move(lay.segs);
+      ids_streamed = std::move(lay.ids);
+      stage_stride = lay.stride;
+      any_defer |= lay.any_defer;
     }
   }
   // Fused group-by (filter_kernel.h fused_defer_gb): a dense key space whose table lives in HBM -- the filter kernel
@@ -4707,16 +4789,6 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // each wave the deepest ring that then fits the 160 KiB LDS (bytes in flight per CU =
   // blocks x 4 waves x (nbuf-1) x slot)
   int nbuf = 0, fbpc = 0;
-  // PHIP_GRID_CUS=n (n >= 1; tests): the CU count every tile-walking launch sizes its grid from, so that a small
-  // input runs the walks with few, long-lived waves (many tiles and segment changes per wave, as at production
-  // sizes). Which kernel variant or walk runs keeps following the device's CU count.
-  int grid_cus = dev->num_cus;
-  if (const char *gc = getenv("PHIP_GRID_CUS")) {
-    if (atoi(gc) >= 1) {
-      grid_cus = atoi(gc);
-      P.sel_max_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * 8);  // (8 workgroups per CU, as the XCD walks' floor)
-    }
-  }
   const int32_t fring_bytes = fused_gb ? 4 * kFusedRingGB : (any_defer ? 4 * kFusedRingDefer : 2 * kFusedRingTile);  // per wave
   {
     const char *env = getenv("PHIP_FILTER_BPC");  // measurement override
@@ -4741,19 +4813,34 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         fbpc = bpc;
       }
     }
-    if (nbuf < 2) return fail(PHIP_ERR_UNSUPPORTED, "filter needs %d bytes of LDS per ring slot", stage_stride);
-    // A small fused query (up to 8 tiles per wave at one workgroup per CU: sorted Q1.2's ~3.8K tiles) runs one
-    // workgroup per CU with the deepest ring: its waves get several tiles each with all their DMAs in flight at once,
-    // instead of 5x the waves with one tile each and a 2-slot ring (Q1.2 fused 39.8 -> 33.6 us, profiles/r05d_q1_small.log;
-    // PHIP_FUSED_SMALL=0 keeps the width rule)
+    // (a single slot per wave only through the small fused scan's shape or the PHIP_FILTER_NBUF override, below)
+    if (nbuf < 2 && small_shape.mode < 0 && filter_nbuf_override() != 1)
+      return fail(PHIP_ERR_UNSUPPORTED, "filter needs %d bytes of LDS per ring slot", stage_stride);
+    // A small fused group-by (up to 8 tiles per wave at one workgroup per CU) runs one workgroup per CU with the
+    // deepest ring: its waves get several tiles each with all their DMAs in flight at once. The rule dates from the
+    // time every wave ended with same-address atomics (profiles/r05d_q1_small.log); fused aggregations have left it
+    // for the residency rule (small_shape, above) except under a forced walk, the fused group-by has not been
+    // re-measured. PHIP_FUSED_SMALL=0 keeps the width rule.
     const char *fs = getenv("PHIP_FUSED_SMALL");
-    if (!env && fused_any && !(fs && atoi(fs) == 0) &&
+    if (!env && fused_any && small_shape.mode < 0 && !(fs && atoi(fs) == 0) &&
         total_work <= (int64_t)dev->num_cus * kFilterWaves * 8 && fbpc > 1) {
       const int64_t nb = std::min<int64_t>(kMaxRing, ((160 * 1024) - static_lds - fring) / ((int64_t)kFilterWaves * stage_stride));
       if (nb >= 2) {
         nbuf = (int)nb;
         fbpc = 1;
       }
+    }
+    if (small_shape.mode >= 0) {  // (computed with this slot, doc ring and static LDS: a fused aggregation)
+      nbuf = small_shape.nbuf;
+      fbpc = small_shape.bpc;
+    } else if (const int fn = filter_nbuf_override()) {
+      // PHIP_FILTER_NBUF on any other plan: this depth at the widest grid whose workgroups then share the LDS
+      fbpc = 0;
+      for (int bpc = want; bpc >= 1 && fbpc == 0; bpc--)
+        if (((160 * 1024) / bpc - static_lds - fring) / ((int64_t)kFilterWaves * stage_stride) >= fn) fbpc = bpc;
+      if (fbpc == 0)
+        return fail(PHIP_ERR_UNSUPPORTED, "PHIP_FILTER_NBUF=%d: %d ring slots of %d bytes per wave exceed the LDS", fn, fn, stage_stride);
+      nbuf = fn;
     }
   }
   const size_t filter_lds = (size_t)kFilterWaves * nbuf * stage_stride + (fused_any ? (size_t)kFilterWaves * fring_bytes : 0) +
@@ -4767,6 +4854,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   if (const char *mt = getenv("PHIP_FILTER_MIN_TILES")) min_tiles_per_wave = std::max(1, atoi(mt));  // A/B
   int filter_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)grid_cus * fbpc,
                                                                   ceil_div(total_work, kFilterWaves * min_tiles_per_wave)));
+  // (the small fused scan: the workgroups of its shape -- all resident; a device's CU count times any workgroups per CU
+  // is a multiple of 8, so the XCD walk's rounding keeps them so)
+  if (small_shape.mode >= 0) filter_blocks = small_shape.blocks;
   if (xcd_walk) filter_blocks = (int)round_up(std::max(filter_blocks, 8), 8);
 
   // ---- aggregation kernel configuration (aggregate.hip) -----------------------------------------
