@@ -124,3 +124,59 @@ def test_zstd_malformed_rejected(zlib_):
         b[i] ^= int(rng.integers(1, 256))
         n = zlib_.phip_test_zstd(bytes(b), len(b), out, len(data))
         assert n in (-1, len(data))
+
+
+# ---- frames of more than one zstd block (128 KiB): Pinot's derived var-byte chunks are 1 MiB by default -----------
+@pytest.fixture(scope="module")
+def big_chunks():
+    from tests.chunk_streams import var_byte_chunk, word_rows
+    rng = np.random.default_rng(42)
+    low = bytes(rng.integers(0, 4, 300_000, dtype=np.uint8) * 17)  # 2 bits of entropy per byte: Huffman literals
+    rows = [w.encode() for w in word_rows(22_000)]
+    strings = var_byte_chunk(rows, len(rows))                       # 88 000 start-offset bytes + the words: ~440 KB
+    assert len(strings) > 400_000
+    return [low, strings, bytes(300_000)]
+
+
+@pytest.mark.parametrize("level", [0, 1, 6, 9])
+def test_gzip_big_chunks_match_zlib(lib, big_chunks, level):
+    for data in big_chunks:
+        comp = pinot_gzip(data, level)
+        out = ctypes.create_string_buffer(len(data))
+        n = lib.phip_test_pinot_gzip(comp, len(comp), out, len(data))
+        assert n == len(data) and out.raw == data, (level, len(data), n)
+
+
+def test_gzip_big_chunks_fixed_and_stored_blocks(lib, big_chunks):
+    for data in big_chunks:
+        for strategy in (zlib.Z_FIXED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE, zlib.Z_FILTERED):
+            c = zlib.compressobj(6, zlib.DEFLATED, 15, 9, strategy)
+            comp = c.compress(data) + c.flush() + len(data).to_bytes(4, "big")
+            out = ctypes.create_string_buffer(len(data))
+            assert lib.phip_test_pinot_gzip(comp, len(comp), out, len(data)) == len(data), (strategy, len(data))
+            assert out.raw == data
+
+
+def zstd_blocks(frame):
+    """Block count of a single-segment-or-not zstd frame (RFC 8878 §3.1.1: magic, frame header, 3-byte block
+    headers with the last-block bit)."""
+    fhd = frame[4]
+    single, dict_id = (fhd >> 5) & 1, (0, 1, 2, 4)[fhd & 3]
+    fcs = (0, 2, 4, 8)[fhd >> 6] or single
+    p, blocks = 5 + (0 if single else 1) + dict_id + fcs, 0
+    while True:
+        h = int.from_bytes(frame[p:p + 3], "little")
+        blocks += 1
+        p += 3 + (1 if (h >> 1) & 3 == 1 else h >> 3)  # an RLE block stores one byte
+        if h & 1:
+            return blocks
+
+
+@pytest.mark.parametrize("level", [-5, 1, 3, 9, 19, 22])
+def test_zstd_big_chunks_match_libzstd(zlib_, big_chunks, level):
+    for data in big_chunks:
+        comp = zstd_compress(data, level)
+        assert zstd_blocks(comp) >= 3  # 300 000 bytes and more: at least three 128 KiB blocks
+        out = ctypes.create_string_buffer(len(data))
+        n = zlib_.phip_test_zstd(comp, len(comp), out, len(data))
+        assert n == len(data) and out.raw == data, (level, len(data), n)
