@@ -151,6 +151,38 @@ typedef struct phip_segment_desc {
  * exclusive). With enableNullHandling the host composes these with the other leaves (BaseColumnFilterOperator's
  * trues AND NOT nulls, the And / Or / Not operators' getFalses), so the library needs nothing else for nulls. */
 #define PHIP_LEAF_NULL 10
+/* REGEXP_LIKE / LIKE over a raw STRING column (RegexpLikePredicateEvaluatorFactory's RawValueBasedRegexpLike-
+ * PredicateEvaluator, RegexpLikePredicateEvaluatorFactory.java:108-110: Matcher.reset(value).find() per scanned doc;
+ * LIKE arrives as REGEXP_LIKE, RequestContextUtils.java:231-236). ids points at `count` int32 words holding a DFA
+ * blob (below); a doc matches when the DFA accepts the value's UTF-8 bytes (xor exclusive). The library walks the DFA
+ * over the column's resident bytes in a pass of its own before the filter launch (strmatch.hip) and hands the filter
+ * kernels dense doc words, as for an inverted leaf. numEntriesScannedInFilter counts num_docs per such leaf of every
+ * unpruned (segment, program) entry: ScanBasedFilterOperator scans every doc (FilterOperatorUtils.java:108-117 makes a
+ * REGEXP_LIKE leaf without an FST index a scan, whatever other index the column has). */
+#define PHIP_LEAF_RAW_STRING_MATCH 11
+
+/* ---- DFA blob -----------------------------------------------------------------------------
+ * A complete deterministic automaton over bytes with find() semantics built in (the caller's compiler adds the
+ * unanchored prefix loop and the absorbing accept state): a value matches when the walk from `start` over all its
+ * bytes ends in an accepting state. int32 words, little-endian:
+ *   [0] PHIP_STRMATCH_VERSION   [1] S = states   [2] C = byte classes   [3] start state
+ *   ceil(S / 32) accept words: bit s % 32 of word s / 32 = state s accepts
+ *   64 words = 256 bytes: the class (< C) of every byte value
+ *   S x C uint16 transitions, row-major (state, class) -> state (< S), padded with one zero u16 to a whole word
+ * The library checks every field before any launch (PHIP_ERR_INVALID otherwise): the version, 1 <= S <=
+ * PHIP_STRMATCH_MAX_STATES, 1 <= C <= 256, S x C x 2 <= PHIP_STRMATCH_MAX_TABLE_BYTES, start < S, every class < C,
+ * every transition < S, and that `count` is exactly the blob's word count; no kernel depends on the caller for staying
+ * inside its table. A Java caller can fill the blob from Lucene's ByteRunAutomaton.
+ * The caps are what one workgroup's LDS holds beside the waves' staging windows with two workgroups resident per CU. */
+#define PHIP_STRMATCH_VERSION 1
+#define PHIP_STRMATCH_MAX_STATES 4096
+#define PHIP_STRMATCH_MAX_TABLE_BYTES 65536
+
+/* In phip_filter_node.exclusive of a DICT_RANGE / DICT_SET leaf: keep the leaf a scan of the forward index even when its
+ * ids are none or all of the dictionary's, where the library otherwise folds it to MATCH_NONE / MATCH_ALL and may prune
+ * the segment. A dictionary REGEXP_LIKE leaf sets it: the reference's evaluator is never always-true / always-false and
+ * its leaf always scans (FilterOperatorUtils.java:108-117), so numEntriesScannedInFilter counts the scan. */
+#define PHIP_LEAF_FLAG_ALWAYS_SCAN 2
 
 typedef struct phip_raw_range {
   int64_t lo_int, hi_int; /* INT/LONG columns: lo_int <= v <= hi_int */
@@ -164,7 +196,8 @@ typedef struct phip_filter_node {
   int32_t leaf_kind;    /* PHIP_LEAF_* */
   int32_t column;       /* index into phip_query_desc.columns */
   int32_t lo, hi;       /* DICT_RANGE */
-  int32_t exclusive;    /* DICT_SET / INVERTED */
+  int32_t exclusive;    /* DICT_SET / INVERTED / RAW_SET / RAW_STRING_SET / RAW_STRING_MATCH / NULL: bit 0 = match the
+                         * complement; DICT_RANGE / DICT_SET: | PHIP_LEAF_FLAG_ALWAYS_SCAN */
   int32_t count;        /* number of ids (DICT_SET/INVERTED) or of ranges (DOC_RANGES) */
   const int32_t *ids;
 } phip_filter_node;
@@ -528,6 +561,18 @@ PHIP_API int32_t phip_runtime_versions(int32_t *out_built, int32_t *out_runtime)
 PHIP_API int32_t phip_segment_load(const phip_segment_desc *desc, uint64_t *out_handle);
 PHIP_API int32_t phip_segment_unload(uint64_t handle);
 PHIP_API int32_t phip_segment_device_bytes(uint64_t handle, uint64_t *out_bytes);
+/* REGEXP_LIKE / LIKE over a dictionary STRING column (single- or multi-value): runs the DFA blob `dfa` (dfa_words int32
+ * words, "DFA blob" above) once over the column's `cardinality` dictionary entries instead of the docs
+ * (RegexpLikePredicateEvaluatorFactory's DictionaryBasedRegexpLikePredicateEvaluator looks the value up and matches it
+ * per scanned doc, RegexpLikePredicateEvaluatorFactory.java:74-76). Bit i % 64 of out_words[i / 64] is set iff entry i
+ * matches; bits at and past the cardinality are 0. An entry is the bytes before its first 0 pad byte, or all
+ * string_width of them (FixedByteValueReaderWriter.readUnpaddedBytes). num_words must be >= ceil(cardinality / 64).
+ * The caller turns the ids into DICT_RANGE / DICT_SET leaves. The dictionary's bytes are uploaded on the first call
+ * and stay with the segment (phip_segment_device_bytes then includes them). Errors: PHIP_ERR_INVALID for a bad blob,
+ * a column that is not a dictionary STRING column, or too few words; PHIP_ERR_UNSUPPORTED in a library built without
+ * the kernel. */
+PHIP_API int32_t phip_segment_match_dictionary(uint64_t handle, const char *column, const int32_t *dfa, int32_t dfa_words,
+                                               uint64_t *out_words, int64_t num_words);
 /* The segment's derived value columns (phip_query_desc.derived): how many it holds now (at most 16), their bytes, and
  * the materialise launches since load -- a plan whose expression the segment already holds launches none.
  * phip_segment_device_bytes stays what the segment's load pinned: it does not include these bytes (nor the other
@@ -704,7 +749,9 @@ PHIP_API int32_t phip_plan_exchange(uint64_t plan, int32_t *out_parts, int32_t *
                                          * = matched; saturates at INT32_MAX) */
 #define PHIP_SHAPE_DISTINCT_ROWS_REGIME 11 /* SELECT DISTINCT: how the plan keeps its key set -- 0 not a distinct plan, 1
                                            * a bitmap in every workgroup's LDS, 2 a global bitmap, 3 sorted keys */
-#define PHIP_LAUNCH_SHAPE_VALUES 12
+#define PHIP_SHAPE_MATCH_TASKS 12 /* RAW_STRING_MATCH leaves (one task per leaf of an unpruned segment x program entry)
+                                   * the string-match launch of the execution walked; 0: no such launch */
+#define PHIP_LAUNCH_SHAPE_VALUES 13
 PHIP_API int32_t phip_plan_launch_shape(uint64_t plan, int32_t *out_shape, int32_t num_values);
 
 #endif /* PINOT_HIP_H_ */

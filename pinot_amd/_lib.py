@@ -22,7 +22,10 @@ PHIP_ERR_CANCELLED = 7
 FWD_FIXED_BIT, FWD_SORTED, FWD_RAW_CHUNK, FWD_HLL_REGISTERS, FWD_FIXED_BIT_MV = 0, 1, 2, 3, 4
 NODE_LEAF, NODE_AND, NODE_OR, NODE_NOT = 0, 1, 2, 3
 LEAF_MATCH_ALL, LEAF_MATCH_NONE, LEAF_DICT_RANGE, LEAF_DICT_SET, LEAF_DOC_RANGES, LEAF_INVERTED, LEAF_RAW_RANGE, \
-    LEAF_RAW_SET, LEAF_RAW_STRING_RANGE, LEAF_RAW_STRING_SET, LEAF_NULL = range(11)
+    LEAF_RAW_SET, LEAF_RAW_STRING_RANGE, LEAF_RAW_STRING_SET, LEAF_NULL, LEAF_RAW_STRING_MATCH = range(12)
+LEAF_FLAG_ALWAYS_SCAN = 2  # in FilterNode.exclusive of a DICT_RANGE / DICT_SET leaf (PHIP_LEAF_FLAG_ALWAYS_SCAN)
+# the DFA blob's version and caps (include/pinot_hip.h PHIP_STRMATCH_*; query/regex_dfa.py compiles within them)
+STRMATCH_VERSION, STRMATCH_MAX_STATES, STRMATCH_MAX_TABLE_BYTES = 1, 4096, 65536
 
 
 class RawRange(ctypes.Structure):
@@ -47,7 +50,7 @@ EXPORTED_SYMBOLS = (
     "phip_plan_destroy", "phip_global_dictionary", "phip_plan_execute_partial", "phip_plan_finish",
     "phip_runtime_versions", "phip_plan_abandon_partial", "phip_result_select_dictionary",
     "phip_plan_set_deadline", "phip_plan_cancel", "phip_plan_exchange", "phip_result_distinct_dictionary",
-    "phip_plan_launch_shape", "phip_segment_derived_info",
+    "phip_plan_launch_shape", "phip_segment_derived_info", "phip_segment_match_dictionary",
 )
 
 # phip_plan_exchange kinds (include/pinot_hip.h "node plans")
@@ -60,7 +63,7 @@ EXCHANGE_HASH = 4
 # phip_plan_launch_shape values, in order (include/pinot_hip.h PHIP_SHAPE_*)
 LAUNCH_SHAPE_FIELDS = ("total_work", "filter_blocks", "agg_blocks", "agg_waves", "nbuf", "num_work_segments",
                        "distinct_blocks", "select_blocks", "fused_lean", "host_final", "select_candidates",
-                       "distinct_rows_regime")
+                       "distinct_rows_regime", "match_tasks")
 # phip_plan_launch_shape's distinct_rows_regime (include/pinot_hip.h PHIP_SHAPE_DISTINCT_ROWS_REGIME)
 DISTINCT_ROWS_NONE, DISTINCT_ROWS_LDS, DISTINCT_ROWS_GLOBAL, DISTINCT_ROWS_SORTED = range(4)
 DISTINCT_ROWS_MAX_COLUMNS = 8  # device.h kMaxDistinctRowCols
@@ -267,6 +270,8 @@ def load(with_torch: bool = False):
     lib.phip_segment_device_bytes.restype = i32
     lib.phip_segment_derived_info.argtypes = [u64, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.phip_segment_derived_info.restype = i32
+    lib.phip_segment_match_dictionary.argtypes = [u64, ctypes.c_char_p, ctypes.POINTER(i32), i32, ctypes.POINTER(u64), i64]
+    lib.phip_segment_match_dictionary.restype = i32
     lib.phip_query.argtypes = [ctypes.POINTER(QueryDesc), ctypes.POINTER(ctypes.POINTER(Result))]
     lib.phip_query.restype = i32
     lib.phip_result_dictionary.argtypes = [ctypes.POINTER(Result), i32, ctypes.POINTER(DictionaryView)]

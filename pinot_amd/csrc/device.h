@@ -208,6 +208,36 @@ struct MvReduceTask {
   int32_t pad;
 };
 
+// String matching (REGEXP_LIKE / LIKE; strmatch.hip strmatch_kernel; include/pinot_hip.h "DFA blob"). One task = one DFA
+// over `num` strings: a raw STRING column's docs (element d = bytes [offsets[d], offsets[d + 1]) of `bytes`) or a
+// dictionary's entries (offsets == null: element i = the `width` bytes at i * width, ending at its first 0 byte). The
+// kernel writes the task's dense element words (bit e % 64 of u64 word e / 64; tile t's 32 words at out + t *
+// tile_words) for tiles [0, num_tiles) -- every word, zeros past `num`; `invert` stores the complement within `num`.
+// The table is the library's validated, renumbered image of the blob (runtime.cpp strmatch_image): `trans` holds S x C
+// u16 entries PRE-MULTIPLIED by C (a state is its row's first index, so a byte costs trans[state + cmap[byte]]), the
+// states are ordered dead (absorbing, not accepting) < absorbing accepting < other accepting < the rest, so "the walk
+// can stop" is state < absorb_end and "accepted" is accept_begin <= state < accept_end, one compare each. Every entry
+// is < S x C: the walk stays inside the table whatever the bytes are.
+constexpr int kStrMatchMaxStates = 4096;              // PHIP_STRMATCH_MAX_STATES
+constexpr int kStrMatchMaxTableBytes = 65536;         // PHIP_STRMATCH_MAX_TABLE_BYTES
+constexpr int kStrMatchWindow = 2048;                 // bytes of a wave's LDS staging window
+struct StrMatchTask {
+  const uint8_t *bytes;
+  const uint64_t *offsets;  // null: a dictionary
+  const uint32_t *table;    // the device image: 64 words of class map, then the S x C u16 transitions
+  uint64_t *out;
+  int32_t tile_words;
+  int32_t num;
+  int32_t num_tiles;
+  int32_t tile_begin;  // the task's first tile among all tasks' tiles (the grid-stride work list)
+  int32_t width;       // dictionary: bytes per entry
+  int32_t num_states, num_classes;
+  int32_t start;                      // pre-multiplied by C, like the three bounds below
+  int32_t absorb_end;                 // states below it are absorbing
+  int32_t accept_begin, accept_end;   // the accepting states
+  int32_t invert;
+};
+
 // One group-by column's key id source for the tuple packing of key spaces above 2^62 (keys.hip tuple_words_kernel).
 constexpr int kMaxTupleCols = 8;
 constexpr int kMaxTupleWords = 4;

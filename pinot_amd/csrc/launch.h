@@ -171,6 +171,16 @@ struct MvLaunchers {
 };
 void register_mv_launchers(const MvLaunchers *l);  // defined in runtime.cpp
 
+// ---- strmatch.hip (REGEXP_LIKE / LIKE) ---------------------------------------------------------------------------
+// Registered like ExprLauncher (null in the host simulation: a RAW_STRING_MATCH leaf or phip_segment_match_dictionary
+// is then PHIP_ERR_UNSUPPORTED). match: `tasks` in device memory, total_tiles = the sum of their num_tiles, on at most
+// max_blocks workgroups; table_words = the largest task's table image in u32 words (it sizes the launch's LDS).
+struct StrMatchLaunchers {
+  hipError_t (*match)(const StrMatchTask *tasks, int32_t ntasks, int32_t total_tiles, int32_t table_words,
+                      int max_blocks, hipStream_t s);
+};
+void register_strmatch_launchers(const StrMatchLaunchers *l);  // defined in runtime.cpp
+
 // ---- distinct_rows.hip (SELECT DISTINCT) -------------------------------------------------------------------------
 // Registered like ExprLauncher (null in the host simulation: a distinct query is then PHIP_ERR_UNSUPPORTED).
 // mark: one pass over the matched docs on at most max_blocks workgroups; DR_LDS / DR_GLOBAL set the docs' key bits in

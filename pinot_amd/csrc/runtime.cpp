@@ -302,6 +302,7 @@ struct ColumnStore {
   int64_t total_values = 0;
   int32_t max_values = 0;
   std::vector<uint8_t> host_dict;  // dictionary bytes as given (BE / padded strings)
+  uint8_t *dict_bytes = nullptr;   // STRING dictionary: host_dict resident (phip_segment_match_dictionary), on first use
   std::vector<int32_t> sorted_pairs;  // sorted columns: (start,end) per dict id
   std::map<int, uint32_t *> hll;      // per log2m
   std::map<int, uint32_t *> hll_doc;  // per log2m: doc-order copy of hll (ensure_hll_doc), in the segment's allocations
@@ -343,6 +344,8 @@ struct DerivedBuf {
 static phip::ExprLauncher g_expr_launcher = nullptr;
 // mv.hip's launchers (launch.h MvLaunchers): null in a library without the kernel unit
 static const phip::MvLaunchers *g_mv = nullptr;
+// strmatch.hip's launcher (launch.h StrMatchLaunchers): null in a library without the kernel unit
+static const phip::StrMatchLaunchers *g_strmatch = nullptr;
 // select_order.hip's launchers (launch.h SelectOrderLaunchers): null in a library without the kernel unit
 static const phip::SelectOrderLaunchers *g_sel_order = nullptr;
 // distinct_rows.hip's launchers (launch.h DistinctRowsLaunchers): null in a library without the kernel unit
@@ -1134,7 +1137,7 @@ int validate_tree(const phip_filter_node *nodes, int begin, int end, int idx, in
   int after;
   switch (n.op) {
     case PHIP_NODE_LEAF:
-      if (n.leaf_kind < PHIP_LEAF_MATCH_ALL || n.leaf_kind > PHIP_LEAF_NULL) {
+      if (n.leaf_kind < PHIP_LEAF_MATCH_ALL || n.leaf_kind > PHIP_LEAF_RAW_STRING_MATCH) {
         err = "bad leaf kind";
         return -1;
       }
@@ -1155,6 +1158,10 @@ int validate_tree(const phip_filter_node *nodes, int begin, int end, int idx, in
       if ((n.leaf_kind == PHIP_LEAF_RAW_STRING_RANGE && (n.ids == nullptr || n.count < 4 || n.count > (1 << 24))) ||
           (n.leaf_kind == PHIP_LEAF_RAW_STRING_SET && (n.ids == nullptr || n.count < 2 || n.count > (1 << 26)))) {
         err = "raw STRING leaf: count words of bounds / values (<= 2^24 / 2^26)";
+        return -1;
+      }
+      if (n.leaf_kind == PHIP_LEAF_RAW_STRING_MATCH && (n.ids == nullptr || n.count < 4)) {
+        err = "raw STRING match leaf needs a DFA blob";
         return -1;
       }
       if ((n.leaf_kind == PHIP_LEAF_DICT_SET || n.leaf_kind == PHIP_LEAF_INVERTED || n.leaf_kind == PHIP_LEAF_DOC_RANGES ||
@@ -2094,6 +2101,11 @@ struct Plan {
   int32_t mv_total_tiles = 0;
   int mv_max_blocks = 1;
   int64_t mv_entries = 0;
+  // RAW_STRING_MATCH leaves (strmatch.hip strmatch_kernel): the same for their tasks; sm_entries = num_docs per leaf
+  // of every unpruned (segment, program) entry whose program counts (ScanBasedFilterOperator scans every doc)
+  size_t sm_tasks_off = 0, num_sm_tasks = 0;
+  int32_t sm_total_tiles = 0, sm_table_words = 0;
+  int64_t sm_entries = 0;
   void *inv_words = nullptr;
   size_t inv_words_total = 0;
   void *fpart = nullptr, *finals = nullptr, *seg_matched = nullptr, *apart = nullptr, *masks = nullptr;
@@ -2238,6 +2250,57 @@ struct AuxFix {  // a leaf's node.aux = device base of the plan's blob + off
   size_t node;
   size_t off;
 };
+
+// A validated DFA blob (include/pinot_hip.h "DFA blob") as the kernel reads it (device.h StrMatchTask): `words` = the
+// 64 words of class map, then the S x C u16 transitions pre-multiplied by C over renumbered states -- dead (absorbing,
+// not accepting) first, then absorbing accepting, then the other accepting states, then the rest -- so the kernel's
+// "stop" and "accepted" tests are one compare each. Every check the header promises happens here, before any launch.
+struct StrMatchImage {
+  std::vector<uint32_t> words;
+  int32_t num_states = 0, num_classes = 0, start = 0, absorb_end = 0, accept_begin = 0, accept_end = 0;
+};
+static int32_t strmatch_image(const int32_t *blob, int64_t nwords, StrMatchImage *out) {
+  if (blob == nullptr || nwords < 4) return fail(PHIP_ERR_INVALID, "DFA blob: shorter than its header");
+  if (blob[0] != PHIP_STRMATCH_VERSION) return fail(PHIP_ERR_INVALID, "DFA blob: version %d, expected %d", blob[0], PHIP_STRMATCH_VERSION);
+  const int64_t S = blob[1], C = blob[2], start = blob[3];
+  if (S < 1 || S > PHIP_STRMATCH_MAX_STATES || C < 1 || C > 256 || S * C * 2 > PHIP_STRMATCH_MAX_TABLE_BYTES)
+    return fail(PHIP_ERR_INVALID, "DFA blob: %lld states x %lld classes outside the caps (%d states, %d table bytes)",
+                (long long)S, (long long)C, PHIP_STRMATCH_MAX_STATES, PHIP_STRMATCH_MAX_TABLE_BYTES);
+  if (start < 0 || start >= S) return fail(PHIP_ERR_INVALID, "DFA blob: start state %lld of %lld", (long long)start, (long long)S);
+  const int64_t aw = (S + 31) / 32, need = 4 + aw + 64 + (S * C + 1) / 2;
+  if (nwords != need) return fail(PHIP_ERR_INVALID, "DFA blob: %lld words, its header says %lld", (long long)nwords, (long long)need);
+  const uint32_t *acc = (const uint32_t *)blob + 4;
+  const uint8_t *cmap = (const uint8_t *)(blob + 4 + aw);
+  const uint16_t *tr = (const uint16_t *)(blob + 4 + aw + 64);
+  for (int b = 0; b < 256; b++)
+    if (cmap[b] >= C) return fail(PHIP_ERR_INVALID, "DFA blob: byte %d has class %d of %lld", b, (int)cmap[b], (long long)C);
+  for (int64_t i = 0; i < S * C; i++)
+    if (tr[i] >= S) return fail(PHIP_ERR_INVALID, "DFA blob: transition %lld leads to state %d of %lld", (long long)i, (int)tr[i], (long long)S);
+  // rank: 0 dead, 1 absorbing accepting, 2 accepting, 3 the rest
+  std::vector<int32_t> rank(S), perm(S);
+  int32_t cnt[4] = {0, 0, 0, 0};
+  for (int64_t st = 0; st < S; st++) {
+    bool absorbing = true;
+    for (int64_t c = 0; c < C && absorbing; c++) absorbing = tr[st * C + c] == st;
+    const bool accepting = (acc[st >> 5] >> (st & 31)) & 1u;
+    rank[st] = absorbing ? (accepting ? 1 : 0) : (accepting ? 2 : 3);
+    cnt[rank[st]]++;
+  }
+  int32_t base[4] = {0, cnt[0], cnt[0] + cnt[1], cnt[0] + cnt[1] + cnt[2]};
+  for (int64_t st = 0; st < S; st++) perm[st] = base[rank[st]]++;
+  out->words.assign(64 + (S * C + 1) / 2, 0u);
+  memcpy(out->words.data(), cmap, 256);
+  uint16_t *ot = (uint16_t *)(out->words.data() + 64);
+  for (int64_t st = 0; st < S; st++)
+    for (int64_t c = 0; c < C; c++) ot[(int64_t)perm[st] * C + c] = (uint16_t)(perm[tr[st * C + c]] * C);
+  out->num_states = (int32_t)S;
+  out->num_classes = (int32_t)C;
+  out->start = (int32_t)(perm[start] * C);
+  out->accept_begin = (int32_t)(cnt[0] * C);
+  out->absorb_end = (int32_t)((cnt[0] + cnt[1]) * C);
+  out->accept_end = (int32_t)((cnt[0] + cnt[1] + cnt[2]) * C);
+  return PHIP_OK;
+}
 
 static int32_t raw_string_leaf(const phip_filter_node &fn, DevNode &dn, Blob &blob, std::vector<AuxFix> &aux_fix,
                                size_t ni) {
@@ -2408,6 +2471,7 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
 // ================================================================================================
 void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
 void phip::register_mv_launchers(const MvLaunchers *l) { g_mv = l; }
+void phip::register_strmatch_launchers(const StrMatchLaunchers *l) { g_strmatch = l; }
 void phip::register_select_order_launchers(const SelectOrderLaunchers *l) { g_sel_order = l; }
 void phip::register_distinct_rows_launchers(const DistinctRowsLaunchers *l) { g_distinct_rows = l; }
 // the filter kernels of this library store records (filter.hip registers it; false in a build without the kernel units,
@@ -3728,6 +3792,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     int32_t mv_lo = 0, mv_hi = 0, mv_invert = 0, mv_set_words = 0;
     size_t mv_set_off = 0;  // the id bitmap in the blob (mv_set_words > 0)
     bool mv_stats = false;  // the leaf's program counts in numEntriesScannedInFilter
+    // a RAW_STRING_MATCH leaf: its doc words come from strmatch_kernel (mv_invert / mv_stats as for an MV leaf)
+    bool sm = false;
+    size_t sm_table_off = 0;  // the table image in the blob
+    int32_t sm_table_words = 0, sm_states = 0, sm_classes = 0, sm_start = 0, sm_absorb_end = 0, sm_accept_begin = 0,
+            sm_accept_end = 0;
   };
   std::vector<bool> entry_has_work;  // per (segment, program) entry
   std::vector<InvLeaf> inv_leaves;
@@ -3853,7 +3922,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         }
         int slot = 0;
         for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
-        InvLeaf L{ni, s, colidx[s][fn.column], &fn, num_entries, slot};
+        InvLeaf L{ni, s, colidx[s][fn.column], nullptr, num_entries, slot};  // (src: the inverted leaves' ids only)
         L.mv = true;
         L.mv_lo = lo;
         L.mv_hi = hi;
@@ -3868,8 +3937,32 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         dn.count = 0;
         dn.bits = 0;
       };
+      // An always-scan leaf over a single-value column whose ids are none or all of the dictionary's: a set leaf that
+      // matches no / every id (a range [0, card) would shift its span out of the id width when card == 2^bits, which
+      // is why such a range is otherwise folded to MATCH_ALL)
+      auto scan_const = [&](DevNode &dn, size_t ni, const ColumnStore &c, bool all) {
+        dn.leaf_kind = PHIP_LEAF_DICT_SET;
+        dn.lo = dn.hi = 0;
+        dn.exclusive = 0;
+        dn.bs_nruns = 0;
+        if (c.card <= 64) {
+          dn.small_set = 1;
+          dn.set_mask = all ? ~0ull : 0ull;
+        } else {
+          std::vector<uint32_t> b(ceil_div(c.card, 32) + 1, all ? ~0u : 0u);
+          dn.count = (int32_t)b.size();
+          aux_fix.push_back({ni, blob.add(b.data(), b.size() * 4)});
+        }
+      };
       // leaf -> device node
-      auto make_leaf = [&](const phip_filter_node &fn) -> DevNode {
+      auto make_leaf = [&](const phip_filter_node &src) -> DevNode {
+        // PHIP_LEAF_FLAG_ALWAYS_SCAN (a dictionary REGEXP_LIKE leaf): the leaf stays a scan of the forward index even
+        // when its ids are none or all of the dictionary's, so the segment is not pruned and the scan is counted
+        phip_filter_node flagless = src;
+        flagless.exclusive = src.exclusive & 1;
+        const phip_filter_node &fn = flagless;
+        const bool always_scan = (src.exclusive & PHIP_LEAF_FLAG_ALWAYS_SCAN) != 0 &&
+                                 (src.leaf_kind == PHIP_LEAF_DICT_RANGE || src.leaf_kind == PHIP_LEAF_DICT_SET);
         DevNode dn;
         memset(&dn, 0, sizeof(dn));
         dn.op = DOP_LEAF;
@@ -3891,11 +3984,19 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             if (no_dict(*cs)) { rc = fail(PHIP_ERR_INVALID, "dict leaf on raw column"); break; }
             dn.lo = std::max(0, fn.lo);
             dn.hi = std::min(cs->card, fn.hi);
+            if (always_scan && dn.hi <= dn.lo) {  // (no id to scan for: the empty id set says it)
+              rc = fail(PHIP_ERR_INVALID, "an always-scan DICT_RANGE leaf must hold an id: send an empty DICT_SET");
+              break;
+            }
             if (is_mv(*cs)) {  // ANY value in the range (every doc has a value: the whole dictionary matches all)
-              if (dn.hi <= dn.lo) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-              else if (dn.lo == 0 && dn.hi == cs->card) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+              if (dn.hi <= dn.lo && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+              else if (dn.lo == 0 && dn.hi == cs->card && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
               else mv_leaf(dn, ni, fn, dn.lo, dn.hi, nullptr);
               dn.exclusive = 0;
+              break;
+            }
+            if (always_scan) {
+              if (dn.lo == 0 && dn.hi == cs->card) scan_const(dn, ni, *cs, !fn.exclusive);
               break;
             }
             if (dn.hi <= dn.lo) dn.leaf_kind = PHIP_LEAF_MATCH_NONE;
@@ -3919,8 +4020,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             if (is_mv(*cs)) {
               // inclusive: ANY value in the set; exclusive: NO value in it -- the complement of the inclusive doc set,
               // never "any value outside the set" (so an exclusive set is not rewritten into its complement's range)
-              if (n_in == 0) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-              else if (n_in == cs->card) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+              if (n_in == 0 && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+              else if (n_in == cs->card && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
               else if (contiguous) mv_leaf(dn, ni, fn, mn, mx + 1, nullptr);
               else mv_leaf(dn, ni, fn, 0, 0, &bits);
               dn.exclusive = 0;
@@ -3941,7 +4042,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
               }
               dn.bs_nruns = nr <= 4 && cs->card <= 65536 ? nr : 0;
             }
-            if (n_in == 0) {
+            if (always_scan && (n_in == 0 || n_in == cs->card)) {
+              scan_const(dn, ni, *cs, (n_in != 0) != (fn.exclusive != 0));
+            } else if (n_in == 0) {
               dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
             } else if (n_in == cs->card) {
               dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
@@ -4029,6 +4132,41 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             }
             rc = raw_string_leaf(fn, dn, blob, aux_fix, ni);
             break;
+          case PHIP_LEAF_RAW_STRING_MATCH: {
+            // REGEXP_LIKE / LIKE over a raw STRING column: evaluated by strmatch_kernel before the filter launch into
+            // dense doc words in the entry's interleaved inverted region; the device node is an inverted leaf over them
+            if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK || cs->type != PHIP_TYPE_STRING || cs->str_off == nullptr) {
+              rc = fail(PHIP_ERR_INVALID, "raw STRING match leaf on column %s, which holds no raw STRING values", cs->name.c_str());
+              break;
+            }
+            StrMatchImage img;
+            if ((rc = strmatch_image(fn.ids, fn.count, &img))) break;
+            if (!g_strmatch) {
+              rc = fail(PHIP_ERR_UNSUPPORTED, "a match leaf over column %s: this library was built without the string-match "
+                        "kernel", cs->name.c_str());
+              break;
+            }
+            int slot = 0;
+            for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
+            InvLeaf L{ni, s, colidx[s][fn.column], nullptr, num_entries, slot};
+            L.sm = true;
+            L.mv_invert = fn.exclusive ? 1 : 0;
+            L.mv_stats = q->stats_programs == 0 || ((q->stats_programs >> prog) & 1u);
+            L.sm_table_words = (int32_t)img.words.size();
+            L.sm_table_off = blob.add(img.words.data(), img.words.size() * 4);
+            L.sm_states = img.num_states;
+            L.sm_classes = img.num_classes;
+            L.sm_start = img.start;
+            L.sm_absorb_end = img.absorb_end;
+            L.sm_accept_begin = img.accept_begin;
+            L.sm_accept_end = img.accept_end;
+            inv_leaves.push_back(L);
+            dn.leaf_kind = PHIP_LEAF_INVERTED;
+            dn.exclusive = 0;
+            dn.count = 0;
+            dn.bits = 0;
+            break;
+          }
           case PHIP_LEAF_NULL:
             // the column's resident null doc words, read like an inverted leaf's words (one 256-byte region per tile)
             if (cs->nulls == nullptr) {
@@ -4047,7 +4185,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             {
               int slot = 0;
               for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
-              inv_leaves.push_back({ni, s, colidx[s][fn.column], &fn, num_entries, slot});
+              inv_leaves.push_back({ni, s, colidx[s][fn.column], &src, num_entries, slot});
             }
             break;
           default: break;
@@ -4199,6 +4337,10 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   std::vector<MvScanTask> mv_tasks;
   std::vector<size_t> mv_set_offs;
   int64_t mv_total_tiles = 0, mv_entries = 0;
+  std::vector<StrMatchTask> sm_tasks;
+  std::vector<size_t> sm_table_offs;
+  int64_t sm_total_tiles = 0, sm_entries = 0;
+  int32_t sm_table_words = 0;
   for (size_t i = 0; i < inv_leaves.size(); i++) {
     const InvLeaf &L = inv_leaves[i];
     const ColumnStore &cs = segs[L.seg]->cols[L.col];
@@ -4230,6 +4372,32 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       if (L.mv_stats) mv_entries += cs.total_values;
       mv_tasks.push_back(t);
       mv_set_offs.push_back(L.mv_set_words > 0 ? L.mv_set_off : SIZE_MAX);
+      continue;
+    }
+    if (L.sm) {
+      if (!entry_has_work[L.entry]) continue;  // (a pruned entry: no tile reads the words)
+      StrMatchTask t;
+      memset(&t, 0, sizeof(t));
+      t.bytes = (const uint8_t *)cs.raw;
+      t.offsets = cs.str_off;
+      t.out = words;
+      t.tile_words = tile_words;
+      t.num = segs[L.seg]->num_docs;
+      t.num_tiles = (int32_t)(inv_word_nw[i] / 32);
+      t.tile_begin = (int32_t)sm_total_tiles;
+      t.num_states = L.sm_states;
+      t.num_classes = L.sm_classes;
+      t.start = L.sm_start;
+      t.absorb_end = L.sm_absorb_end;
+      t.accept_begin = L.sm_accept_begin;
+      t.accept_end = L.sm_accept_end;
+      t.invert = L.mv_invert;
+      sm_total_tiles += t.num_tiles;
+      if (sm_total_tiles > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many string-match tiles in one query");
+      if (L.mv_stats) sm_entries += segs[L.seg]->num_docs;
+      sm_table_words = std::max(sm_table_words, L.sm_table_words);
+      sm_tasks.push_back(t);
+      sm_table_offs.push_back(L.sm_table_off);
       continue;
     }
     const size_t first = tasks.size();
@@ -4272,6 +4440,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   const size_t tasks_off = tasks.empty() ? 0 : blob.add(tasks.data(), tasks.size() * sizeof(RoaringTask));
   const size_t rgroups_off = rgroups.empty() ? 0 : blob.add(rgroups.data(), rgroups.size() * sizeof(RoaringGroup));
   const size_t mv_tasks_off = mv_tasks.empty() ? 0 : blob.reserve(mv_tasks.size() * sizeof(MvScanTask));
+  const size_t sm_tasks_off = sm_tasks.empty() ? 0 : blob.reserve(sm_tasks.size() * sizeof(StrMatchTask));
 
   // ---- filter kernel configuration (filter.hip) -------------------------------------------------
   // Per 2048-doc tile, the wave's ring slot receives the fixed-bit words of every scanned filter column
@@ -4987,6 +5156,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   for (size_t i = 0; i < mv_tasks.size(); i++)
     if (mv_set_offs[i] != SIZE_MAX) mv_tasks[i].set = (const uint32_t *)(base + mv_set_offs[i]);
   if (!mv_tasks.empty()) memcpy(blob.data.data() + mv_tasks_off, mv_tasks.data(), mv_tasks.size() * sizeof(MvScanTask));
+  for (size_t i = 0; i < sm_tasks.size(); i++) sm_tasks[i].table = (const uint32_t *)(base + sm_table_offs[i]);
+  if (!sm_tasks.empty()) memcpy(blob.data.data() + sm_tasks_off, sm_tasks.data(), sm_tasks.size() * sizeof(StrMatchTask));
   if (!nodes.empty()) memcpy(blob.data.data() + nodes_off, nodes.data(), nodes.size() * sizeof(DevNode));
   if (!dsegs.empty()) memcpy(blob.data.data() + segs_off, dsegs.data(), sizeof(DevSeg) * dsegs.size());
   const DevSeg *dev_segs = (const DevSeg *)(base + segs_off);
@@ -5369,6 +5540,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   P.mv_total_tiles = (int32_t)mv_total_tiles;
   P.mv_max_blocks = std::max(1, grid_cus * 8);
   P.mv_entries = mv_entries;
+  P.sm_tasks_off = sm_tasks_off;
+  P.num_sm_tasks = sm_tasks.size();
+  P.sm_total_tiles = (int32_t)sm_total_tiles;
+  P.sm_table_words = sm_table_words;
+  P.sm_entries = sm_entries;
   P.dq_off = dq_off;
   P.kinds_off = kinds_off;
   P.inv_words = inv_words;
@@ -5544,6 +5720,9 @@ static int32_t enqueue_plan(Plan &P, hipStream_t st) {
   if (P.num_mv_tasks)  // the MV scan leaves' doc words, beside the inverted leaves' (every word of every leaf written)
     HIP_TRY(g_mv->scan((const MvScanTask *)(base + P.mv_tasks_off), (int32_t)P.num_mv_tasks, P.mv_total_tiles,
                        P.mv_max_blocks, st));
+  if (P.num_sm_tasks)  // the match leaves' doc words, likewise: one launch over all of them
+    HIP_TRY(g_strmatch->match((const StrMatchTask *)(base + P.sm_tasks_off), (int32_t)P.num_sm_tasks, P.sm_total_tiles,
+                              P.sm_table_words, P.mv_max_blocks, st));
   if (group_by && dq.mode == GB_HASH) {
     HIP_TRY(hipMemsetAsync(dq.gb_keys, 0xff, (size_t)dq.num_groups * 8, st));  // kHashEmpty
     HIP_TRY(hipMemsetAsync(dq.hash_overflow, 0, 4, st));
@@ -6170,7 +6349,8 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   if (mode != EXEC_FINISH) {
     const int32_t sh[PHIP_LAUNCH_SHAPE_VALUES] = {(int32_t)P.total_work, P.filter_blocks, P.agg_blocks, P.dq.wg_waves,
                                                   P.fq.nbuf, (int32_t)P.dsegs.size(), P.dist_blocks, P.sel_max_blocks,
-                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0, 0, P.drq.regime};
+                                                  P.variant == FV_FUSED_LEAN ? 1 : 0, 0, 0, P.drq.regime,
+                                                  (int32_t)P.num_sm_tasks};
     memcpy(P.shape, sh, sizeof(sh));
   }
   if (P.graph_exec) {
@@ -6213,7 +6393,8 @@ static int32_t execute_plan(Plan &P, phip_result **out_result, uint64_t *filter_
   auto local_stats = [&](int64_t st6[6]) {
     const int64_t m = has_filter ? (int64_t)fin[32] : docs_in_work;
     st6[0] = m;  // several programs: summed over them (FilteredAggregationOperator adds its infos' statistics)
-    st6[1] = has_filter ? (int64_t)fin[33] + P.mv_entries : 0;  // (an MV scan leaf: its values, counted at plan time)
+    // (an MV scan leaf: its values; a match leaf: its docs -- both counted at plan time)
+    st6[1] = has_filter ? (int64_t)fin[33] + P.mv_entries + P.sm_entries : 0;
     st6[2] = m * num_projected;
     st6[3] = total_docs;
     st6[4] = nseg;
@@ -7157,6 +7338,89 @@ PHIP_API int32_t phip_segment_device_bytes(uint64_t handle, uint64_t *out_bytes)
   auto it = g_segments.find(handle);
   if (it == g_segments.end()) return fail(PHIP_ERR_NOT_FOUND, "unknown segment handle");
   if (out_bytes) *out_bytes = it->second->device_bytes;
+  return PHIP_OK;
+}
+
+// REGEXP_LIKE / LIKE over a dictionary STRING column: the DFA over the dictionary's entries (strmatch.hip, the dictionary
+// locator). The padded dictionary bytes go to the device on the first call and stay in the segment's allocations.
+PHIP_API int32_t phip_segment_match_dictionary(uint64_t handle, const char *column, const int32_t *dfa, int32_t dfa_words,
+                                               uint64_t *out_words, int64_t num_words) {
+  if (!column || !out_words || num_words < 0) return fail(PHIP_ERR_INVALID, "null argument");
+  StrMatchImage img;
+  int32_t rc = strmatch_image(dfa, dfa_words, &img);
+  if (rc) return rc;
+  std::shared_ptr<Segment> seg;
+  Device *dev;
+  {
+    std::lock_guard<std::mutex> g(g_mu);
+    auto it = g_segments.find(handle);
+    if (it == g_segments.end()) return fail(PHIP_ERR_NOT_FOUND, "unknown segment handle");
+    seg = it->second;
+    dev = find_device(seg->device);
+  }
+  if (!dev) return fail(PHIP_ERR_NO_DEVICE, "device %d not initialised", seg->device);
+  auto ci = seg->by_name.find(column);
+  if (ci == seg->by_name.end()) return fail(PHIP_ERR_NOT_FOUND, "segment %s has no column %s", seg->name.c_str(), column);
+  ColumnStore &cs = seg->cols[ci->second];
+  if (cs.type != PHIP_TYPE_STRING || no_dict(cs) || cs.string_width <= 0 ||
+      cs.host_dict.size() != (size_t)cs.card * (size_t)cs.string_width)
+    return fail(PHIP_ERR_INVALID, "column %s is not a dictionary STRING column", column);
+  const int64_t need = ((int64_t)cs.card + 63) / 64;
+  if (num_words < need) return fail(PHIP_ERR_INVALID, "column %s: %lld words for %d dictionary entries", column, (long long)num_words, cs.card);
+  if (!g_strmatch)
+    return fail(PHIP_ERR_UNSUPPORTED, "a dictionary match over column %s: this library was built without the string-match "
+                "kernel", column);
+  memset(out_words, 0, (size_t)num_words * 8);
+  if (cs.card == 0) return PHIP_OK;
+  std::lock_guard<std::mutex> dl(dev->mu);
+  HIP_TRY(hipSetDevice(dev->ordinal));
+  hipStream_t st = dev->stream;
+  if (cs.dict_bytes == nullptr) {  // (16 bytes of padding: the kernel stages whole 16-byte pieces)
+    void *p;
+    if ((rc = dev_alloc(*seg, cs.host_dict.size() + 16, &p))) return rc;
+    HIP_TRY(hipMemsetAsync((uint8_t *)p + cs.host_dict.size(), 0, 16, st));
+    HIP_TRY(hipMemcpyAsync(p, cs.host_dict.data(), cs.host_dict.size(), hipMemcpyHostToDevice, st));
+    cs.dict_bytes = (uint8_t *)p;
+  }
+  const int32_t ntiles = (int32_t)(((int64_t)cs.card + kTileDocs - 1) / kTileDocs);
+  const size_t table_off = round_up((int64_t)sizeof(StrMatchTask), 16);
+  const size_t out_off = round_up((int64_t)(table_off + img.words.size() * 4), 16);
+  const size_t total = out_off + (size_t)ntiles * 32 * 8;
+  void *tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, total));
+  struct Free {
+    void *p;
+    ~Free() { (void)hipFree(p); }
+  } free_tmp{tmp};
+  StrMatchTask t;
+  memset(&t, 0, sizeof(t));
+  t.bytes = cs.dict_bytes;
+  t.offsets = nullptr;
+  t.table = (const uint32_t *)((uint8_t *)tmp + table_off);
+  t.out = (uint64_t *)((uint8_t *)tmp + out_off);
+  t.tile_words = 32;
+  t.num = cs.card;
+  t.num_tiles = ntiles;
+  t.tile_begin = 0;
+  t.width = cs.string_width;
+  t.num_states = img.num_states;
+  t.num_classes = img.num_classes;
+  t.start = img.start;
+  t.absorb_end = img.absorb_end;
+  t.accept_begin = img.accept_begin;
+  t.accept_end = img.accept_end;
+  std::vector<uint8_t> stage(out_off, 0);
+  memcpy(stage.data(), &t, sizeof(t));
+  memcpy(stage.data() + table_off, img.words.data(), img.words.size() * 4);
+  HIP_TRY(hipMemcpyAsync(tmp, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+  int grid_cus = dev->num_cus;
+  if (const char *gc = getenv("PHIP_GRID_CUS"))
+    if (atoi(gc) >= 1) grid_cus = atoi(gc);
+  hipError_t e = g_strmatch->match((const StrMatchTask *)tmp, 1, ntiles, (int32_t)img.words.size(), std::max(1, grid_cus * 8), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_words, t.out, (size_t)need * 8, hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);  // (the staging vector and tmp outlive the copies)
+  HIP_TRY(e);
+  HIP_TRY(e2);
   return PHIP_OK;
 }
 

@@ -26,6 +26,7 @@ import numpy as np
 
 from .. import _lib
 from ..query import predicate as predeval
+from ..query import regex_dfa
 from ..query.context import (MV_AGGREGATIONS, REFUSED_MV_AGGREGATIONS, UNBOUNDED, AggregationInfo, FilterClause,
                              FilterContext, Function, Identifier, Literal, Predicate, QueryContext, columns_of, sv_twin)
 from ..query.sql import parse
@@ -49,6 +50,7 @@ class _Leaf:
     hi: int = 0
     exclusive: bool = False
     ids: Optional[np.ndarray] = None  # int32
+    pattern: bool = False  # a REGEXP_LIKE / LIKE leaf over a dictionary column: never merged with EQ / IN leaves
 
 
 @dataclass
@@ -90,6 +92,10 @@ def _raw_string_predicate(column, pred):
     def words(b: bytes) -> np.ndarray:
         return np.frombuffer(b + b"\0" * (-len(b) % 4), dtype=np.int32).copy()
 
+    if pred.type == "REGEXP_LIKE":
+        # RawValueBasedRegexpLikePredicateEvaluator (RegexpLikePredicateEvaluatorFactory.java:108-110): the pattern's
+        # DFA blob; the library walks it over the column's bytes before the filter launch
+        return _Leaf(_lib.LEAF_RAW_STRING_MATCH, column, ids=regex_dfa.compile_pattern(pred.values[0]).to_blob())
     if pred.type == "RANGE":
         lo = None if pred.lower == UNBOUNDED else str(pred.lower).encode("utf-8")
         hi = None if pred.upper == UNBOUNDED else str(pred.upper).encode("utf-8")
@@ -180,7 +186,36 @@ def _null_leaf(seg: GpuSegment, column: str, exclusive: bool = False):
     return _TRUE if exclusive else _FALSE
 
 
+class PatternTypeError(ValueError):
+    """REGEXP_LIKE / LIKE over a column that is not STRING (the reference's Preconditions check of dataType == STRING
+    in RegexpLikePredicateEvaluatorFactory, answered as a bad query)."""
+
+
+def _match_predicate(seg: GpuSegment, pred):
+    """REGEXP_LIKE / LIKE. A raw STRING column: the RAW_STRING_MATCH leaf. A dictionary column: the DFA runs over the
+    dictionary's entries, not the docs, and the matching ids feed a forward-index scan leaf -- DICT_RANGE when they
+    are contiguous, else DICT_SET, an empty set included -- whatever other index the column has and never a constant:
+    the reference's evaluator is never always-true / always-false and FilterOperatorUtils.java:108-117 makes the leaf
+    a ScanBasedFilterOperator even on a sorted or inverted column, so numEntriesScannedInFilter stays the
+    reference's. A multi-value column gets any-match through the MV scan leaf over the same ids (applyMV)."""
+    if not isinstance(pred.lhs, Identifier):
+        raise UnsupportedOnGpu(f"REGEXP_LIKE / LIKE over the expression {pred.lhs}: columns only on the GPU path")
+    column = pred.column
+    m = seg.column_metadata(column)
+    if m.data_type != DataType.STRING or getattr(m, "hll_log2m", 0):
+        raise PatternTypeError(f"REGEXP_LIKE / LIKE over column {column} of type {DataType(m.data_type).name}: STRING only")
+    if not m.has_dictionary:
+        return _raw_string_predicate(column, pred)
+    pattern = pred.values[0]
+    ids = seg.match_dictionary(column, pattern, regex_dfa.compile_pattern(pattern))
+    if len(ids) and int(ids[-1]) - int(ids[0]) + 1 == len(ids):
+        return _Leaf(_lib.LEAF_DICT_RANGE, column, lo=int(ids[0]), hi=int(ids[-1]) + 1, pattern=True)
+    return _Leaf(_lib.LEAF_DICT_SET, column, ids=np.asarray(ids, dtype=np.int32), pattern=True)
+
+
 def compile_predicate(seg: GpuSegment, pred) -> object:
+    if pred.type == "REGEXP_LIKE":
+        return _match_predicate(seg, pred)
     column = pred.column
     if pred.type in ("IS_NULL", "IS_NOT_NULL"):
         return _null_leaf(seg, column, pred.type == "IS_NOT_NULL")
@@ -240,8 +275,9 @@ def _fold_not(k):
         return _FALSE
     if _is_const(k, _FALSE):
         return _TRUE
-    if isinstance(k, _Leaf) and k.kind in (_lib.LEAF_DICT_SET, _lib.LEAF_INVERTED, _lib.LEAF_RAW_SET, _lib.LEAF_NULL):
-        return _Leaf(k.kind, k.column, k.lo, k.hi, not k.exclusive, k.ids)
+    if isinstance(k, _Leaf) and k.kind in (_lib.LEAF_DICT_SET, _lib.LEAF_INVERTED, _lib.LEAF_RAW_SET, _lib.LEAF_NULL,
+                                             _lib.LEAF_RAW_STRING_MATCH):
+        return _Leaf(k.kind, k.column, k.lo, k.hi, not k.exclusive, k.ids, k.pattern)
     return _Node(_lib.NODE_NOT, [k])
 
 
@@ -307,8 +343,9 @@ def compile_filter(seg: GpuSegment, fc: Optional[FilterContext], null_handling: 
             return _FALSE
         if _is_const(c, _FALSE):
             return _TRUE
-        if isinstance(c, _Leaf) and c.kind in (_lib.LEAF_DICT_SET, _lib.LEAF_INVERTED, _lib.LEAF_RAW_SET, _lib.LEAF_NULL):
-            return _Leaf(c.kind, c.column, c.lo, c.hi, not c.exclusive, c.ids)
+        if isinstance(c, _Leaf) and c.kind in (_lib.LEAF_DICT_SET, _lib.LEAF_INVERTED, _lib.LEAF_RAW_SET, _lib.LEAF_NULL,
+                                                 _lib.LEAF_RAW_STRING_MATCH):
+            return _Leaf(c.kind, c.column, c.lo, c.hi, not c.exclusive, c.ids, c.pattern)
         return _Node(_lib.NODE_NOT, [c])
     kids = [compile_filter(seg, c) for c in fc.children]
     if fc.type == "AND":
@@ -321,7 +358,7 @@ def compile_filter(seg: GpuSegment, fc: Optional[FilterContext], null_handling: 
             return kids[0]
         # evaluation order (FilterOperatorUtils :205-252): sorted < bitmap < scan
         prio = {_lib.LEAF_DOC_RANGES: 0, _lib.LEAF_INVERTED: 1, _lib.LEAF_DICT_RANGE: 3, _lib.LEAF_DICT_SET: 3,
-                _lib.LEAF_RAW_RANGE: 3, _lib.LEAF_RAW_SET: 3}
+                _lib.LEAF_RAW_RANGE: 3, _lib.LEAF_RAW_SET: 3, _lib.LEAF_RAW_STRING_MATCH: 3}
         kids.sort(key=lambda k: prio.get(k.kind, 2) if isinstance(k, _Leaf) else (4 if k.op == _lib.NODE_AND else 5))
         return _Node(_lib.NODE_AND, kids)
     if fc.type == "OR":
@@ -357,7 +394,8 @@ def _merge_or_leaves(kids, mergeable=None):
     groups, order = {}, []
     for i, k in enumerate(kids):
         fam = None
-        if isinstance(k, _Leaf) and k.column is not None and not k.exclusive and (mergeable is None or mergeable[i]):
+        if isinstance(k, _Leaf) and k.column is not None and not k.exclusive and not k.pattern and \
+                (mergeable is None or mergeable[i]):
             fam = "scan" if k.kind in scan else ("inv" if k.kind == _lib.LEAF_INVERTED else None)
         key = (k.column, fam) if fam else id(k)
         if key not in groups:
@@ -382,7 +420,7 @@ def _flatten(tree, col_index, out, keep):
         n.leaf_kind = tree.kind
         n.column = col_index[tree.column] if tree.column is not None else -1
         n.lo, n.hi = tree.lo, tree.hi
-        n.exclusive = int(tree.exclusive)
+        n.exclusive = int(tree.exclusive) | (_lib.LEAF_FLAG_ALWAYS_SCAN if tree.pattern else 0)
         if tree.ids is not None:
             ids = np.ascontiguousarray(tree.ids, dtype=np.int32)
             keep.append(ids)

@@ -6,6 +6,7 @@ PhysicalColumnIndexContainer.java:44-68) — and keeps the host-side readers the
 (dictionaries for predicate evaluation, the sorted index for doc ranges).
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -13,6 +14,11 @@ from .. import _lib
 from ..segment.creator import ImmutableSegment, read_chunk_forward
 from ..segment.dictionary import Dictionary
 from ..spi import DataType
+
+# Dictionaries below this cardinality are matched on the host (Dfa.match_many over the padded dictionary matrix), the
+# others on the device (phip_segment_match_dictionary). PINOT_AMD_STRMATCH_HOST_CARD overrides it: 0 = always the
+# device, a huge value = always the host. Measured crossover: DESIGN.md §3 "String matching".
+STRMATCH_HOST_CARD = 256
 
 
 class GpuSegment:
@@ -27,6 +33,7 @@ class GpuSegment:
         self._inv_offsets = {}
         self._specials = {}  # column -> (holds NaN, holds an infinity): real_specials
         self._intervals = {}  # column -> (min, max) or None: value_interval
+        self._matches = {}  # (column, pattern) -> matching dict ids: match_dictionary
         cols = list(segment.columns.values())
         descs = (_lib.ColumnDesc * max(len(cols), 1))()
         keep = []
@@ -138,6 +145,32 @@ class GpuSegment:
             v = v[~np.isnan(v)]
             self._intervals[column] = (float(v.min()), float(v.max())) if len(v) else None
         return self._intervals[column]
+
+    def match_dictionary(self, column, pattern, dfa) -> np.ndarray:
+        """Sorted int32 dict ids of the dictionary STRING column's entries that ``dfa`` (query.regex_dfa.Dfa, compiled
+        from ``pattern``) accepts -- what the reference's DictionaryBasedRegexpLikePredicateEvaluator finds out per
+        scanned doc (RegexpLikePredicateEvaluatorFactory.java:74-76), once per entry. Kept per (column, pattern)."""
+        key = (column, pattern)
+        ids = self._matches.get(key)
+        if ids is None:
+            ci = self.segment.columns[column]
+            m = ci.metadata
+            card, width = m.cardinality, m.string_width
+            host_card = int(os.environ.get("PINOT_AMD_STRMATCH_HOST_CARD", STRMATCH_HOST_CARD))
+            if card < host_card:
+                mat = np.frombuffer(ci.dictionary, dtype=np.uint8, count=card * width).reshape(card, width)
+                hit = dfa.match_many(mat) if card else np.zeros(0, dtype=bool)
+            else:
+                blob = np.ascontiguousarray(dfa.to_blob(), dtype=np.int32)
+                words = np.zeros(max((card + 63) // 64, 1), dtype=np.uint64)
+                _lib.check(_lib.load().phip_segment_match_dictionary(
+                    self.handle, column.encode(), blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(blob),
+                    words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(words)))
+                hit = np.unpackbits(words.view(np.uint8), bitorder="little")[:card].astype(bool)
+            ids = np.flatnonzero(hit).astype(np.int32)
+            if len(self._matches) < 1024:
+                self._matches[key] = ids
+        return ids
 
     def derived_info(self):
         """(count, bytes, builds) of the segment's derived value columns (phip_segment_derived_info): how many it holds,

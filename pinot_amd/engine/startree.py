@@ -61,6 +61,12 @@ def _matching(seg, pred, negated):
     return ~mask if negated else mask
 
 
+def _has_pattern_predicate(fc) -> bool:
+    if fc.type == "PREDICATE":
+        return fc.predicate.type == "REGEXP_LIKE"
+    return any(_has_pattern_predicate(c) for c in fc.children)
+
+
 def predicate_map(seg, fc) -> Optional[Dict[str, List[tuple]]]:
     """extractPredicateEvaluatorsMap for one segment: column -> list of composite predicates (each a list of
     (predicate, negated) OR-ed together; the list is AND-ed), or None when the filter cannot use the star-tree
@@ -69,6 +75,8 @@ def predicate_map(seg, fc) -> Optional[Dict[str, List[tuple]]]:
     out: Dict[str, List[tuple]] = {}
     if fc is None:
         return out
+    if _has_pattern_predicate(fc):  # REGEXP_LIKE / LIKE: the base segment answers (equal results)
+        return None
     queue = deque([fc])
     while queue:
         n = queue.popleft()

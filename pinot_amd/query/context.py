@@ -13,6 +13,8 @@ from dataclasses import dataclass, field
 from decimal import Decimal
 from typing import List, Optional, Tuple, Union
 
+from .._lib import UnsupportedOnGpu
+
 
 # ----------------------------------------------------------------------------- expressions
 @dataclass(frozen=True)
@@ -80,6 +82,9 @@ class PredicateType:
     RANGE = "RANGE"
     IS_NULL = "IS_NULL"          # the column's null value vector (FilterPlanNode.java:294-307)
     IS_NOT_NULL = "IS_NOT_NULL"
+    # REGEXP_LIKE(col, 'pattern'), values = (pattern,); col LIKE 'p' arrives as REGEXP_LIKE(col, like_to_regexp_like(p))
+    # (RequestContextUtils.java:231-236)
+    REGEXP_LIKE = "REGEXP_LIKE"
 
 
 UNBOUNDED = "*"  # RangePredicate.UNBOUNDED
@@ -89,7 +94,7 @@ UNBOUNDED = "*"  # RangePredicate.UNBOUNDED
 class Predicate:
     type: str
     lhs: Expression
-    values: Tuple = ()                 # EQ/NOT_EQ: (v,), IN/NOT_IN: (v1, ...)
+    values: Tuple = ()                 # EQ/NOT_EQ: (v,), IN/NOT_IN: (v1, ...), REGEXP_LIKE: (pattern,)
     lower: object = UNBOUNDED          # RANGE
     upper: object = UNBOUNDED
     lower_inclusive: bool = False
@@ -98,6 +103,8 @@ class Predicate:
     @property
     def column(self) -> str:
         if not isinstance(self.lhs, Identifier):
+            if self.type == PredicateType.REGEXP_LIKE:
+                raise UnsupportedOnGpu(f"REGEXP_LIKE / LIKE over the expression {self.lhs}: columns only on the GPU path")
             raise NotImplementedError("predicates on expressions are out of scope")
         return self.lhs.name
 

@@ -4,7 +4,7 @@ The reference compiles SQL with Calcite (CalciteSqlParser, pinot-common/.../sql/
 PinotQuery, then QueryContextConverterUtils builds a QueryContext. This is a recursive-descent
 parser for the subset the parity tests and SSB use: SELECT [DISTINCT] <aggregations / group columns>
 FROM t [WHERE <boolean expr>] [GROUP BY ...] [ORDER BY ...] [LIMIT n [OFFSET m] | LIMIT m, n], with predicates
-=, <>, !=, <, <=, >, >=, [NOT] BETWEEN, [NOT] IN, IS [NOT] NULL and NOT/AND/OR, and +, -, *, / and CAST in
+=, <>, !=, <, <=, >, >=, [NOT] BETWEEN, [NOT] IN, [NOT] LIKE, REGEXP_LIKE(col, 'p'), IS [NOT] NULL and NOT/AND/OR, and +, -, *, / and CAST in
 expressions. The reference optimizer's flattening of nested AND/OR
 (pinot-core/.../query/optimizer/filter/FlattenAndOrFilterOptimizer.java) is applied.
 """
@@ -21,11 +21,52 @@ _TOKEN = re.compile(r"""\s*(?:
 )""", re.VERBOSE)
 
 _KEYWORDS = {"select", "from", "where", "group", "by", "order", "limit", "and", "or", "not", "between",
-             "in", "asc", "desc", "as", "cast", "option", "case", "when", "then", "else", "end", "is", "null"}
+             "in", "asc", "desc", "as", "cast", "option", "case", "when", "then", "else", "end", "is", "null", "like"}
 
 
 class SqlError(ValueError):
     pass
+
+
+# RegexpPatternConverterUtils.REGEXP_METACHARACTERS (pinot-common/.../utils/RegexpPatternConverterUtils.java:36-37)
+_LIKE_METACHARACTERS = "^$.{}[]()*+?|<>-&/"
+
+
+def like_to_regexp_like(like: str) -> str:
+    """LIKE pattern -> REGEXP_LIKE pattern, RegexpPatternConverterUtils.likeToRegexpLike restated
+    (RegexpPatternConverterUtils.java:43-131): leading / trailing runs of % drop the ^ / $ anchor, _ becomes ., an
+    inner % becomes .*, a backslash escapes a following wildcard, and regex metacharacters (and a backslash that
+    escapes no wildcard) are escaped."""
+    start, end, prefix, suffix = 0, len(like), "^", "$"
+    if len(like) == 0:
+        return "^$"
+    if len(like) == 1:
+        if like == "%":
+            return ""
+    else:
+        if like[0] == "%":
+            rest = like.lstrip("%")
+            if not rest:
+                return ""
+            start, prefix = len(like) - len(rest), ""
+        if like[-1] == "%":
+            end, suffix = len(like.rstrip("%")), ""
+    out = [prefix]
+    prev_backslash = False
+    for c in like[start:end]:
+        if c == "_":
+            out.append(c if prev_backslash else ".")
+        elif c == "%":
+            out.append(c if prev_backslash else ".*")
+        else:
+            if c in _LIKE_METACHARACTERS or prev_backslash:
+                out.append("\\")
+            out.append(c)
+        prev_backslash = c == "\\"
+    if prev_backslash:
+        out.append("\\")
+    out.append(suffix)
+    return "".join(out)
 
 
 def _tokenize(sql):
@@ -217,7 +258,9 @@ class _Parser:
                 depth -= 1
                 if depth == 0:
                     return False
-            elif depth == 1 and k == "kw" and v in ("and", "or", "not", "between", "in", "is"):
+            elif depth == 1 and k == "kw" and v in ("and", "or", "not", "between", "in", "is", "like"):
+                return True
+            elif depth == 1 and k == "ident" and str(v).lower() == "regexp_like" and self.toks[j + 1] == ("op", "("):
                 return True
             elif depth == 1 and k == "op" and v in ("=", "<>", "!=", "<", "<=", ">", ">="):
                 return True
@@ -231,6 +274,11 @@ class _Parser:
 
     def predicate(self):
         lhs = self.expr()
+        if isinstance(lhs, Function) and lhs.name == "regexp_like":
+            # REGEXP_LIKE(col, 'pattern') in predicate position (RequestContextUtils.java:225-230)
+            if len(lhs.args) != 2 or not isinstance(lhs.args[1], Literal) or not isinstance(lhs.args[1].value, str):
+                raise SqlError("REGEXP_LIKE takes an expression and a string literal pattern")
+            return FilterContext.PRED(Predicate(PredicateType.REGEXP_LIKE, lhs.args[0], values=(lhs.args[1].value,)))
         if self.accept("kw", "is"):  # IS [NOT] NULL (Predicate.Type.IS_NULL / IS_NOT_NULL)
             neg = bool(self.accept("kw", "not"))
             self.expect("kw", "null")
@@ -251,8 +299,15 @@ class _Parser:
             self.expect("op", ")")
             return FilterContext.PRED(Predicate(PredicateType.NOT_IN if neg else PredicateType.IN, lhs,
                                                 values=tuple(vals)))
+        if self.accept("kw", "like"):
+            # col [NOT] LIKE 'p' -> [NOT] REGEXP_LIKE(col, likeToRegexpLike(p)) (RequestContextUtils.java:231-236)
+            pat = self._lit()
+            if not isinstance(pat, str):
+                raise SqlError("LIKE takes a string literal pattern")
+            p = FilterContext.PRED(Predicate(PredicateType.REGEXP_LIKE, lhs, values=(like_to_regexp_like(pat),)))
+            return FilterContext.NOT(p) if neg else p
         if neg:
-            raise SqlError("NOT must precede BETWEEN or IN")
+            raise SqlError("NOT must precede BETWEEN, IN or LIKE")
         op = self.expect("op")[1]
         v = self._lit()
         if op == "=":
