@@ -22,7 +22,7 @@ enum FilterVariant : int32_t {
                    // frees registers for more resident waves. Every variant below is conjunctive too, and has q.agg set:
   FV_FUSED,        // the aggregation runs inside (no aggregation launch)
   FV_FUSED_LEAN,   // ... in its lean shape (kBsDefer): every segment's program is the bit-sliced conjunction and
-                   // every segment defers its projection -- the host decides (runtime.cpp prepare_plan)
+                   // every segment defers its projection -- the host decides (runtime.cpp configure_fusion)
   FV_GB,           // the dense group-by runs inside, into the HBM table (GB_GLOBAL)
   FV_GB_XCD,       // ... into kXcdCopies XCD-private copies of it (GB_XCD), merged after the launch
   FV_GB_LDS,       // ... into each workgroup's LDS table (GB_LDS), its slabs reduced after the launch

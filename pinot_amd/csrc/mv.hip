@@ -1,5 +1,5 @@
 // mv.hip -- multi-value columns (PHIP_FWD_FIXED_BIT_MV): the filter's MV scan leaf and the aggregations' row-reduction
-// columns (device.h MvScanTask / MvReduceTask; runtime.cpp load_mv_forward, the MV leaves of prepare_plan,
+// columns (device.h MvScanTask / MvReduceTask; runtime.cpp load_mv_forward, PlanBuilder::mv_leaf / stage_inverted_leaves,
 // ensure_derived).
 //
 // Resident layout: the dict ids of all rows bit-packed back to back (a single-value fixed-bit column of total_values

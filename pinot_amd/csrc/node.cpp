@@ -673,7 +673,7 @@ void make_sub(const phip_query_desc *q, const Part &p, bool no_trim, SubDesc &sd
 bool node_wanted(const phip_query_desc *q) {
   if (!q || q->num_segments <= 0 || !q->segments) return false;
   int d0 = 0;
-  if (node_segment_device(q->segments[0], &d0)) return false;  // (prepare_plan reports the unknown handle)
+  if (node_segment_device(q->segments[0], &d0)) return false;  // (resolve_inputs reports the unknown handle)
   for (int i = 1; i < q->num_segments; i++) {
     int d = 0;
     if (node_segment_device(q->segments[i], &d)) return false;

@@ -3,7 +3,7 @@
 //
 // Segment load (ImmutableSegmentLoader.load, pinot-segment-local/.../immutable/
 // ImmutableSegmentLoader.java:155-190,222-280) pins, per column, the forward index, the dictionary
-// and the inverted index in HBM in the layouts the kernels read (kernels.hip header). A query
+// and the inverted index in HBM in the layouts the kernels read (device.h DevCol). A query
 // (InstancePlanMakerImplV2.makeInstancePlan, pinot-core/.../plan/maker/InstancePlanMakerImplV2.java:172-199)
 // runs as: Roaring decode of inverted leaves -> one fused filter/aggregate (or group-by) launch over
 // all segments -> deterministic finalize -> one D2H copy; it replaces the per-segment operators and
@@ -403,7 +403,7 @@ static void init_lanes(Device *d);
 // group-by's GB_XCD mode picks a table copy by HW_REG_XCC_ID & 7 and updates it with workgroup-scope atomics in that
 // XCD's L2, correct only while no two L2 domains of the device share a copy: with at most kXcdCopies XCDs the ids
 // are distinct mod 8 (a partition's XCC ids are a contiguous run). A device reporting more XCDs, or no count at all,
-// keeps the one agent-scope table (prepare_plan).
+// keeps the one agent-scope table (configure_fusion).
 static hipError_t device_xcc_count(int ordinal, int *out) {
   int x = 0;
   if (hipDeviceGetAttribute(&x, hipDeviceAttributeNumberOfXccs, ordinal) != hipSuccess || x <= 0) x = 1 << 30;
@@ -2068,7 +2068,7 @@ struct Plan {
   };
   std::vector<ProjCol> proj;
   bool has_filter = false, need_agg = false, need_mask = false, group_by = false;
-  FilterVariant variant = FV_GENERAL;  // the filter kernel's instantiation (launch.h), decided by prepare_plan
+  FilterVariant variant = FV_GENERAL;  // the filter kernel's instantiation (launch.h), set by finish_completion
   int fused_naggs = 0;                 // FV_FUSED / FV_FUSED_LEAN: the aggregations the filter kernel runs (fused_tile)
   bool fused_agg() const { return variant == FV_FUSED || variant == FV_FUSED_LEAN; }
   bool fused_gb() const { return variant == FV_GB || variant == FV_GB_XCD || variant == FV_GB_LDS; }
@@ -2785,59 +2785,194 @@ int32_t ensure_derived(Segment &sg, const std::vector<Segment *> &segs, const ph
   return PHIP_OK;
 }
 
-}  // namespace
+// Environment overrides of a plan's preparation: read at every plan creation (the tests switch them between plans of
+// one process), never cached. env_off: the "0" that switches a default-on rule off.
+int env_int(const char *name, int def) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : def;
+}
+int64_t env_i64(const char *name, int64_t def) {
+  const char *e = getenv(name);
+  return e ? atoll(e) : def;
+}
+bool env_off(const char *name) {
+  const char *e = getenv(name);
+  return e && atoi(e) == 0;
+}
 
-static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t filter_nwords, Plan &P) {
+// prepare_plan's working state: what only the preparation needs. Its member functions are the phases, in the order
+// prepare_plan calls them; each returns PHIP_OK or the error that ends the preparation (~Plan cleans up). What the
+// Plan keeps is written to P where it is computed and read back from P.
+struct PlanBuilder {
+  PlanBuilder(const phip_query_desc *query, Plan &plan) : q(query), P(plan) {}
 
+  int32_t resolve_inputs();
+  int32_t resolve_derived();
+  int32_t resolve_group_keys();
+  int32_t plan_aggregations();
+  int32_t plan_selection();
+  int32_t plan_group_table();
+  int32_t stage_segments();
+  int32_t stage_columns(int s, DevSeg &ds);
+  int32_t lower_filter_program(int s, int prog, const DevSeg &seg_ds);
+  int32_t make_leaf(int s, int prog, const phip_filter_node &src, DevNode &dn);
+  int32_t mv_leaf(int s, int prog, DevNode &dn, size_t ni, const phip_filter_node &fn, int32_t lo, int32_t hi,
+                  const std::vector<uint32_t> *set);
+  void scan_const(DevNode &dn, size_t ni, const ColumnStore &c, bool all);
+  int32_t size_hash_table();
+  int32_t stage_inverted_leaves();
+  int32_t configure_filter_paths();
+  int32_t configure_fusion();
+  int32_t configure_filter_launch();
+  int32_t configure_aggregation();
+  int32_t allocate();
+  int32_t finish_selection();
+  int32_t finish_trim();
+  int32_t finish_completion();
+
+  // column c of segment s read as raw values (no dictionary, or its doc-order values, packed or typed)
+  bool packed_vals(const ColumnStore &cs) const { return vpack_on && cs.vpack != nullptr; }
+  bool as_raw(int s, int c) const {
+    const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
+    return no_dict(cs) || (use_vals[c] && (packed_vals(cs) || cs.vals != nullptr) && vals_eligible(cs, vals_min));
+  }
+  bool fused_any() const { return P.fused_naggs > 0 || fused_gb; }  // the filter kernel aggregates its own tiles
+  int entry_slot() const {  // the next inverted leaf's index among those of the entry being lowered
+    int slot = 0;
+    for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
+    return slot;
+  }
+
+  struct InvLeaf {
+    size_t node;
+    int seg;
+    int col;
+    const phip_filter_node *src;
+    int entry;  // (segment, program) entry whose program holds the leaf
+    int slot;   // index among that entry's inverted leaves
+    // a range / set leaf over a multi-value column: its doc words come from mv_scan_kernel, not from bitmaps
+    bool mv = false;
+    int32_t mv_lo = 0, mv_hi = 0, mv_invert = 0, mv_set_words = 0;
+    size_t mv_set_off = 0;  // the id bitmap in the blob (mv_set_words > 0)
+    bool mv_stats = false;  // the leaf's program counts in numEntriesScannedInFilter
+    // a RAW_STRING_MATCH leaf: its doc words come from strmatch_kernel (mv_invert / mv_stats as for an MV leaf)
+    bool sm = false;
+    size_t sm_table_off = 0;  // the table image in the blob
+    int32_t sm_table_words = 0, sm_states = 0, sm_classes = 0, sm_start = 0, sm_absorb_end = 0, sm_accept_begin = 0,
+            sm_accept_end = 0;
+  };
+  static constexpr int64_t kSlotBudget = 19 * 1024;  // bytes per ring slot of the filter kernel
+
+  // resolve_inputs / resolve_derived / resolve_group_keys
+  const phip_query_desc *q;  // the query as every later phase sees it: qd, then qv, where a phase rewrote it
+  Plan &P;
+  std::unique_lock<std::mutex> dlock;  // the device's mutex, from resolve_inputs to the builder's end
+  std::vector<Segment *> segp;         // P.segs, as the helpers take them
+  hipStream_t st = nullptr;            // the device's setup stream
+  int nreal = 0, ncols = 0;            // the query's own columns; with the derived value columns
+  std::vector<std::vector<int>> colidx;  // [segment][query column] -> the segment's column
+  phip_query_desc qd, qv;              // q with the aggregations rewritten to derived columns / to one tuple key
+  std::vector<phip_aggregation> derived_aggs;
+  std::vector<std::vector<int>> derived_inputs;  // per column nreal + j: the query columns its program reads
+  // plan_aggregations / plan_selection / plan_group_table
+  std::vector<int32_t> kinds;
+  std::vector<bool> projected;
+  std::vector<uint32_t> proj_progs;  // column -> bit p: program p projects it
+  std::vector<bool> use_vals;        // column read through its segments' doc-order values (ensure_vals)
+  int64_t vals_min = 0;
+  bool vpack_on = false;
+  DevSelQuery sq;
+  DevSelOrder so;
+  int nord = 0;  // selection ORDER BY terms (0 for SELECT DISTINCT: its terms order the keys)
+  std::vector<std::shared_ptr<Device::Remap>> col_remap;
+  std::vector<std::vector<uint64_t>> dr_values;  // per SELECT DISTINCT column: the dictionary as result slots
+  int64_t gb_key_space = 0;
+  bool gb_force_hash = false;
+  // stage_segments / stage_inverted_leaves
+  Blob blob;
+  std::vector<DevNode> nodes;
+  std::vector<AuxFix> aux_fix;       // node.aux = dev_base + off
+  std::vector<bool> entry_has_work;  // per (segment, program) entry
+  std::vector<InvLeaf> inv_leaves;
+  int num_entries = 0;  // (segment, program) entries, pruned ones included
+  bool hll_made = false, hll_doc_on = false;
+  std::vector<bool> hll_doc_used, hll_doc16_used;  // (segment, column): HLL entries read by doc / 16-bit ones
+  bool rec_want = false;
+  int rec_min_fields = kRecMinFields;
+  size_t segs_off = 0, nodes_off = 0;
+  std::vector<int32_t> node_inv_slot, node_inv_leaves;  // per node: an inverted leaf's slot / its entry's leaves
+  std::vector<MvScanTask> mv_tasks;
+  std::vector<size_t> mv_set_offs;
+  std::vector<StrMatchTask> sm_tasks;
+  std::vector<size_t> sm_table_offs;
+  // configure_filter_paths / configure_fusion / configure_filter_launch / configure_aggregation
+  int32_t stage_stride = 0;
+  std::vector<double> seg_est;    // per entry: the program's estimated selectivity
+  std::vector<int32_t> seg_off;   // per entry: the bytes of its ring slot the filter's regions take
+  int grid_cus = 0;
+  bool conj_all = true, any_filter_prog = false, any_defer = false;
+  FusedShape small_shape = {-1, 0, 0, 0, 0};  // mode >= 0: the small fused scan's shape (fused_shape.h)
+  std::vector<bool> ids_streamed;  // (segment, column): fused tiles stream its ids
+  // (finish_completion derives P.variant, and with it P.fused() / P.fused_gb(), from these four and conj_all)
+  bool fused_gb = false, gb_xcd = false, gb_lds = false, fused_lean = false;
+  int64_t gb_lds_bytes = 0;  // the fused LDS table per workgroup
+  int nbuf = 0, fbpc = 0, xcd_walk = 0;
+  int32_t fring_bytes = 0;
+  // allocate / finish_*
+  std::vector<size_t> dr_values_off;
+  const DevSeg *dev_segs = nullptr;
+};
+
+int32_t PlanBuilder::resolve_inputs() {
   if (!q || q->num_segments <= 0 || q->num_columns < 0 || q->num_columns > kMaxQueryColumns)
     return fail(PHIP_ERR_INVALID, "query: need >=1 segment and <= %d columns", kMaxQueryColumns);
   if (q->num_aggregations < 0 || q->num_aggregations > kMaxAggs)
     return fail(PHIP_ERR_UNSUPPORTED, "query: at most %d aggregations on the GPU path", kMaxAggs);
   if (q->num_group_by < 0 || q->num_group_by > kMaxGroupBy)
     return fail(PHIP_ERR_UNSUPPORTED, "query: at most %d group-by columns", kMaxGroupBy);
-  if (q->num_segments > 1 && want_bitmap) return fail(PHIP_ERR_INVALID, "filter bitmap: one segment only");
-  const int nprog = std::max(1, q->num_filter_programs);
-  if (nprog > kMaxPrograms) return fail(PHIP_ERR_UNSUPPORTED, "query: at most %d filter programs", kMaxPrograms);
-  if (nprog > 1 && want_bitmap) return fail(PHIP_ERR_UNSUPPORTED, "several filter programs: no filter bitmap");
+  if (q->num_segments > 1 && P.want_bitmap) return fail(PHIP_ERR_INVALID, "filter bitmap: one segment only");
+  P.nprog = std::max(1, q->num_filter_programs);
+  if (P.nprog > kMaxPrograms) return fail(PHIP_ERR_UNSUPPORTED, "query: at most %d filter programs", kMaxPrograms);
+  if (P.nprog > 1 && P.want_bitmap) return fail(PHIP_ERR_UNSUPPORTED, "several filter programs: no filter bitmap");
 
-  std::vector<Segment *> segs(q->num_segments);
-  Device *dev = nullptr;
+  segp.resize(q->num_segments);
   {
     std::lock_guard<std::mutex> g(g_mu);
     for (int i = 0; i < q->num_segments; i++) {
       auto it = g_segments.find(q->segments[i]);
       if (it == g_segments.end()) return fail(PHIP_ERR_NOT_FOUND, "unknown segment handle %llu", (unsigned long long)q->segments[i]);
-      segs[i] = it->second.get();
+      segp[i] = it->second.get();
       P.segs.push_back(it->second);
-      if (i > 0 && segs[i]->device != segs[0]->device)
+      if (i > 0 && segp[i]->device != segp[0]->device)
         return fail(PHIP_ERR_UNSUPPORTED, "segments of one query must reside on one device");
     }
-    dev = find_device(segs[0]->device);
+    P.dev = find_device(segp[0]->device);
   }
-  if (!dev) return fail(PHIP_ERR_NO_DEVICE, "device %d not initialised", segs[0]->device);
-  std::lock_guard<std::mutex> dlock(dev->mu);
-  HIP_TRY(hipSetDevice(dev->ordinal));
-  hipStream_t st = dev->stream;
-  P.dev = dev;
+  if (!P.dev) return fail(PHIP_ERR_NO_DEVICE, "device %d not initialised", segp[0]->device);
+  dlock = std::unique_lock<std::mutex>(P.dev->mu);
+  HIP_TRY(hipSetDevice(P.dev->ordinal));
+  st = P.dev->stream;
 
-  const int nseg = q->num_segments, nreal = q->num_columns, naggs = q->num_aggregations;
+  P.nseg = q->num_segments;
+  nreal = q->num_columns;
+  P.naggs = q->num_aggregations;
   // resolve columns
-  std::vector<std::vector<int>> colidx(nseg, std::vector<int>(nreal, -1));
-  for (int s = 0; s < nseg; s++)
+  colidx.assign(P.nseg, std::vector<int>(nreal, -1));
+  for (int s = 0; s < P.nseg; s++)
     for (int c = 0; c < nreal; c++) {
-      auto it = segs[s]->by_name.find(q->columns[c]);
-      if (it == segs[s]->by_name.end())
-        return fail(PHIP_ERR_NOT_FOUND, "segment %s has no column %s", segs[s]->name.c_str(), q->columns[c]);
+      auto it = segp[s]->by_name.find(q->columns[c]);
+      if (it == segp[s]->by_name.end())
+        return fail(PHIP_ERR_NOT_FOUND, "segment %s has no column %s", segp[s]->name.c_str(), q->columns[c]);
       colidx[s][c] = it->second;
     }
+  return PHIP_OK;
+}
 
-  // Derived value columns (include/pinot_hip.h phip_expr_op): each (program, value kind) an aggregation reads becomes
-  // one more column of the query -- index nreal + j, a raw LONG / DOUBLE column of every segment, evaluated on first
-  // use (ensure_derived) -- and the aggregation is rewritten to read it. Everything below sees raw columns only; the
-  // programs' own input columns are resolved above and otherwise untouched (not projected, staged or recorded).
-  phip_query_desc qd;
-  std::vector<phip_aggregation> derived_aggs;
-  std::vector<std::vector<int>> derived_inputs;  // per column nreal + j: the query columns its program reads
+// Derived value columns (include/pinot_hip.h phip_expr_op): each (program, value kind) an aggregation reads becomes
+// one more column of the query -- index nreal + j, a raw LONG / DOUBLE column of every segment, evaluated on first
+// use (ensure_derived) -- and the aggregation is rewritten to read it. Every later phase sees raw columns only; the
+// programs' own input columns are resolved by resolve_inputs and otherwise untouched (not projected, staged or recorded).
+int32_t PlanBuilder::resolve_derived() {
   if (q->num_derived < 0 || (q->num_derived > 0 && !q->derived)) return fail(PHIP_ERR_INVALID, "query: bad derived columns");
   if (q->num_derived > 0) {
     const int nd = q->num_derived;
@@ -2851,7 +2986,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     for (int k = 0; k < q->num_group_by && q->group_by_columns; k++)
       if (q->group_by_columns[k] >= nreal) return fail(PHIP_ERR_INVALID, "group-by column %d is a derived column", k);
     if (q->filter_offsets && q->filter_nodes)
-      for (int i = q->filter_offsets[0]; i < q->filter_offsets[nprog * nseg]; i++)
+      for (int i = q->filter_offsets[0]; i < q->filter_offsets[P.nprog * P.nseg]; i++)
         if (q->filter_nodes[i].op == PHIP_NODE_LEAF && q->filter_nodes[i].column >= nreal)
           return fail(PHIP_ERR_INVALID, "filter leaf %d reads a derived column", i);
     for (int k = 0; k < q->num_select && q->select; k++)
@@ -2862,8 +2997,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       int32_t rc = check_expr_program(q, k, info[k]);
       if (rc) return rc;
       for (int c : info[k].cols)
-        for (int s = 0; s < nseg; s++) {
-          const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+        for (int s = 0; s < P.nseg; s++) {
+          const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
           if (cs.type == PHIP_TYPE_STRING)
             return fail(PHIP_ERR_INVALID, "derived column %d: numeric expression over STRING column %s", k, cs.name.c_str());
           if (cs.fwd_kind == PHIP_FWD_HLL_REGISTERS)
@@ -2877,7 +3012,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
             return fail(PHIP_ERR_UNSUPPORTED, "derived column %d: multi-value column %s has no values to reduce", k, cs.name.c_str());
         }
     }
-    derived_aggs.assign(q->aggregations, q->aggregations + (q->aggregations ? naggs : 0));
+    derived_aggs.assign(q->aggregations, q->aggregations + (q->aggregations ? P.naggs : 0));
     struct Use {
       int k;
       bool integral;
@@ -2906,12 +3041,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       if (red == PHIP_MV_REDUCE_MIN || red == PHIP_MV_REDUCE_MAX) u.integral = false;  // (MIN and MAX read doubles)
       if (u.integral) {
         long double bound = 0;
-        u.lo.resize(nseg);
-        u.hi.resize(nseg);
-        for (int s = 0; s < nseg && u.integral; s++) {
+        u.lo.resize(P.nseg);
+        u.hi.resize(P.nseg);
+        for (int s = 0; s < P.nseg && u.integral; s++) {
           if (red != PHIP_MV_REDUCE_NONE) {
             // a row's length is in [1, max_values]; its sum within max_values x [vmin, vmax] (the 2^62 rule per value)
-            const ColumnStore &mc = segs[s]->cols[colidx[s][info[k].cols[0]]];
+            const ColumnStore &mc = segp[s]->cols[colidx[s][info[k].cols[0]]];
             const long double mx = (long double)std::max(mc.max_values, 1);
             if (red == PHIP_MV_REDUCE_LENGTH) {
               u.lo[s] = 1;
@@ -2922,11 +3057,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
               u.hi[s] = std::max<long double>(mx * (long double)mc.vmax, (long double)mc.vmax);
               if (std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) >= (long double)((int64_t)1 << 62)) u.integral = false;
             }
-            if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segs[s]->num_docs;
+            if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segp[s]->num_docs;
             continue;
           }
-          u.integral = expr_int_interval(q->derived[k], *segs[s], colidx[s], &u.lo[s], &u.hi[s]);
-          if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segs[s]->num_docs;
+          u.integral = expr_int_interval(q->derived[k], *segp[s], colidx[s], &u.lo[s], &u.hi[s]);
+          if (u.integral) bound += std::max(fabsl(u.lo[s]), fabsl(u.hi[s])) * (long double)segp[s]->num_docs;
         }
         if (bound >= (long double)((int64_t)1 << 58)) u.integral = false;
       }
@@ -2945,10 +3080,10 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     DerivedJobs jobs;
     for (const Use &u : uses) {
       derived_inputs.push_back(info[u.k].cols);
-      for (int s = 0; s < nseg; s++) {
+      for (int s = 0; s < P.nseg; s++) {
         std::shared_ptr<DerivedBuf> buf;
         int col = -1;
-        int32_t rc = ensure_derived(*segs[s], segs, q->derived[u.k], colidx[s], u.integral, u.integral ? u.lo[s] : 0,
+        int32_t rc = ensure_derived(*segp[s], segp, q->derived[u.k], colidx[s], u.integral, u.integral ? u.lo[s] : 0,
                                     u.integral ? u.hi[s] : 0, jobs, &buf, &col);
         if (rc) {
           drop_derived(jobs);
@@ -2964,12 +3099,15 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     qd.aggregations = derived_aggs.data();
     q = &qd;
   }
-  const int ncols = nreal + (int)derived_inputs.size();
+  ncols = nreal + (int)derived_inputs.size();
+  return PHIP_OK;
+}
 
+int32_t PlanBuilder::resolve_group_keys() {
   // A multi-value column is read by filter leaves and, through a row reduction, by aggregations: nothing else.
-  for (int s = 0; s < nseg; s++) {
+  for (int s = 0; s < P.nseg; s++) {
     auto mv_col = [&](int c) -> const char * {
-      return c >= 0 && c < nreal && is_mv(segs[s]->cols[colidx[s][c]]) ? segs[s]->cols[colidx[s][c]].name.c_str() : nullptr;
+      return c >= 0 && c < nreal && is_mv(segp[s]->cols[colidx[s][c]]) ? segp[s]->cols[colidx[s][c]].name.c_str() : nullptr;
     };
     for (int k = 0; k < q->num_group_by && q->group_by_columns; k++)
       if (const char *nm = mv_col(q->group_by_columns[k]))
@@ -2979,7 +3117,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       if (!nm && q->select[k].expr != PHIP_EXPR_COLUMN) nm = mv_col(q->select[k].column_b);
       if (nm) return fail(PHIP_ERR_UNSUPPORTED, "selecting or ordering by the multi-value column %s", nm);
     }
-    for (int a = 0; a < naggs && q->aggregations; a++) {
+    for (int a = 0; a < P.naggs && q->aggregations; a++) {
       const phip_aggregation &ag = q->aggregations[a];
       if (ag.function == PHIP_AGG_COUNT) continue;
       const char *nm = mv_col(ag.column_a);
@@ -2991,7 +3129,6 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // A group-by whose mixed-radix key space exceeds 2^62 groups by tuple keys (build_tuple_keys): the plan is made for
   // one virtual key column (the first group-by column's slot carries its ids) and execute_plan expands the keys.
   // Device trims that order by a group key need the columns' order, so such a plan returns every group instead.
-  phip_query_desc qv;
   if (q->num_group_by > 1 && q->group_by_columns) {
     std::vector<std::shared_ptr<Device::Remap>> dicts;
     std::vector<int64_t> radix;
@@ -2999,21 +3136,21 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     for (int k = 0; k < q->num_group_by; k++) {
       const int c = q->group_by_columns[k];
       if (c < 0 || c >= ncols) return fail(PHIP_ERR_INVALID, "group_by_columns[%d] = %d out of range", k, c);
-      std::vector<int> ci(nseg);
-      for (int s = 0; s < nseg; s++) ci[s] = colidx[s][c];
+      std::vector<int> ci(P.nseg);
+      for (int s = 0; s < P.nseg; s++) ci[s] = colidx[s][c];
       bool null_key = false;
       if ((q->null_group_by >> k) & 1)
-        for (int s = 0; s < nseg; s++) null_key |= segs[s]->cols[ci[s]].nulls != nullptr;
+        for (int s = 0; s < P.nseg; s++) null_key |= segp[s]->cols[ci[s]].nulls != nullptr;
       std::shared_ptr<Device::Remap> r;
-      int32_t rc = build_remap(*dev, segs, ci, q->columns[c], r, null_key);
+      int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], r, null_key);
       if (rc) return rc;
       dicts.push_back(r);
       radix.push_back((int64_t)r->card + (null_key ? 1 : 0));
       space *= (long double)radix.back();
     }
-    const char *tk = getenv("PHIP_TUPLE_KEYS");  // test override: "1" = tuple keys for any multi-column group-by
-    if (space > (long double)((int64_t)1 << 62) || (tk && atoi(tk) != 0)) {
-      int32_t rc = build_tuple_keys(*dev, segs, colidx, q->group_by_columns, q->num_group_by, dicts, radix,
+    // PHIP_TUPLE_KEYS (test override): "1" = tuple keys for any multi-column group-by
+    if (space > (long double)((int64_t)1 << 62) || env_int("PHIP_TUPLE_KEYS", 0) != 0) {
+      int32_t rc = build_tuple_keys(*P.dev, segp, colidx, q->group_by_columns, q->num_group_by, dicts, radix,
                                     P.tuple_word, P.tuple_stride, P.tuple_remap);
       if (rc) return rc;
       P.tuple_keys = true;
@@ -3035,38 +3172,40 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       q = &qv;
     }
   }
+  return PHIP_OK;
+}
 
-  // aggregations
-  DevAggQuery dq;
-  memset(&dq, 0, sizeof(dq));
-  dq.num_segs = nseg;
-  dq.num_aggs = naggs;
-  int nhll = 0, log2m = 0;
-  std::vector<int32_t> kinds(naggs + 2, ACC_COUNT);
-  std::vector<bool> projected(ncols, false);
-  std::vector<uint32_t> proj_progs(ncols, 0);  // column -> bit p: program p projects it
-  for (int a = 0; a < naggs; a++) {
+// The aggregations: accumulator kinds, exact-sum bounds, the projected columns, the doc-order values of value-only
+// columns, and the walk the aggregation kernel takes over dense tiles.
+int32_t PlanBuilder::plan_aggregations() {
+  memset(&P.dq, 0, sizeof(P.dq));
+  P.dq.num_segs = P.nseg;
+  P.dq.num_aggs = P.naggs;
+  kinds.assign(P.naggs + 2, ACC_COUNT);
+  projected.assign(ncols, false);
+  proj_progs.assign(ncols, 0);
+  for (int a = 0; a < P.naggs; a++) {
     const phip_aggregation &ag = q->aggregations[a];
-    DevAgg &d = dq.aggs[a];
+    DevAgg &d = P.dq.aggs[a];
     d.expr = ag.expr;
     d.col_a = ag.column_a;
     d.col_b = ag.column_b;
-    if (ag.program < 0 || ag.program >= nprog)
-      return fail(PHIP_ERR_INVALID, "aggregation %d: program %d outside [0, %d)", a, ag.program, nprog);
+    if (ag.program < 0 || ag.program >= P.nprog)
+      return fail(PHIP_ERR_INVALID, "aggregation %d: program %d outside [0, %d)", a, ag.program, P.nprog);
     d.program = ag.program;
     if (ag.function < PHIP_AGG_COUNT || ag.function > PHIP_AGG_VALUE_COUNTS) return fail(PHIP_ERR_INVALID, "bad aggregation function");
     if (is_distinct_fn(ag.function)) {  // the refusals of include/pinot_hip.h PHIP_AGG_DISTINCT / PHIP_AGG_VALUE_COUNTS
       const char *fn = distinct_fn_name(ag.function);
       if (ag.expr != PHIP_EXPR_COLUMN) return fail(PHIP_ERR_UNSUPPORTED, "%s of an expression", fn);
-      if (nprog > 1) return fail(PHIP_ERR_UNSUPPORTED, "%s beside several filter programs", fn);
+      if (P.nprog > 1) return fail(PHIP_ERR_UNSUPPORTED, "%s beside several filter programs", fn);
       if (q->null_group_by) return fail(PHIP_ERR_UNSUPPORTED, "%s beside null group keys", fn);
       if (P.tuple_keys) return fail(PHIP_ERR_UNSUPPORTED, "%s over a tuple key space", fn);
       if (tl_node_docs > 0) return fail(PHIP_ERR_UNSUPPORTED, "%s in a node plan", fn);
-      if (want_bitmap || q->num_select > 0) return fail(PHIP_ERR_INVALID, "%s outside an aggregation query", fn);
+      if (P.want_bitmap || q->num_select > 0) return fail(PHIP_ERR_INVALID, "%s outside an aggregation query", fn);
     }
     if (ag.function == PHIP_AGG_VALUE_COUNTS) {  // a u32 count per id: it must not wrap
       int64_t docs = 0;
-      for (int s = 0; s < nseg; s++) docs += segs[s]->num_docs;
+      for (int s = 0; s < P.nseg; s++) docs += segp[s]->num_docs;
       if (docs >= ((int64_t)1 << 32))
         return fail(PHIP_ERR_UNSUPPORTED, "value counts (PERCENTILE / MODE) over %lld docs: a u32 count could wrap", (long long)docs);
     }
@@ -3082,8 +3221,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     }
     bool integral = true;
     if (ag.function != PHIP_AGG_COUNT) {
-      for (int s = 0; s < nseg; s++) {
-        const ColumnStore &ca = segs[s]->cols[colidx[s][ag.column_a]];
+      for (int s = 0; s < P.nseg; s++) {
+        const ColumnStore &ca = segp[s]->cols[colidx[s][ag.column_a]];
         if (!(ca.type == PHIP_TYPE_INT || ca.type == PHIP_TYPE_LONG)) integral = false;
         if (is_distinct_fn(ag.function)) {  // dictionary ids only: any type, but a dictionary in every segment
           if (no_dict(ca) || ca.fwd_kind == PHIP_FWD_HLL_REGISTERS || ca.words == nullptr)
@@ -3107,7 +3246,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         if (ag.function == PHIP_AGG_HLL && ag.expr != PHIP_EXPR_COLUMN && ca.type == PHIP_TYPE_STRING)
           return fail(PHIP_ERR_INVALID, "numeric expression over STRING column");
         if (ag.expr != PHIP_EXPR_COLUMN) {
-          const ColumnStore &cb = segs[s]->cols[colidx[s][ag.column_b]];
+          const ColumnStore &cb = segp[s]->cols[colidx[s][ag.column_b]];
           if (!(cb.type == PHIP_TYPE_INT || cb.type == PHIP_TYPE_LONG)) integral = false;
           if (cb.type == PHIP_TYPE_STRING) return fail(PHIP_ERR_INVALID, "numeric expression over STRING column");
           if (cb.fwd_kind == PHIP_FWD_HLL_REGISTERS)
@@ -3122,17 +3261,17 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       // which cannot wrap. (2^58, not 2^62: the cross-GPU merge all-reduces the exact partials of up to
       // kMaxExactRanks = 16 GPUs as int64 SUM, distributed.allreduce_*, and 16 x 2^58 = 2^62 cannot wrap either.)
       long double bound = 0;
-      for (int s = 0; s < nseg && integral; s++) {
-        const ColumnStore &ca = segs[s]->cols[colidx[s][ag.column_a]];
+      for (int s = 0; s < P.nseg && integral; s++) {
+        const ColumnStore &ca = segp[s]->cols[colidx[s][ag.column_a]];
         auto mag = [](const ColumnStore &c) -> long double {
           return c.has_range ? std::max(fabsl((long double)c.vmin), fabsl((long double)c.vmax)) : 1e30L;
         };
         long double e = mag(ca);
         if (ag.expr != PHIP_EXPR_COLUMN) {
-          const long double b = mag(segs[s]->cols[colidx[s][ag.column_b]]);
+          const long double b = mag(segp[s]->cols[colidx[s][ag.column_b]]);
           e = ag.expr == PHIP_EXPR_MUL ? e * b : e + b;
         }
-        bound += e * (long double)segs[s]->num_docs;
+        bound += e * (long double)segp[s]->num_docs;
       }
       if (bound >= (long double)((int64_t)1 << 58)) integral = false;
     }
@@ -3152,45 +3291,45 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       // with its own log2m, DistinctCountHLLAggregationFunction.java:105-145). One column per entry table, so two
       // log2m over one dictionary column stay on the CPU path (a raw column's values are hashed per function).
       bool raw_everywhere = ag.expr == PHIP_EXPR_COLUMN;
-      for (int s = 0; s < nseg && raw_everywhere; s++) {
-        const ColumnStore &cs = segs[s]->cols[colidx[s][ag.column_a]];
+      for (int s = 0; s < P.nseg && raw_everywhere; s++) {
+        const ColumnStore &cs = segp[s]->cols[colidx[s][ag.column_a]];
         raw_everywhere = cs.fwd_kind == PHIP_FWD_RAW_CHUNK;
       }
       for (int b = 0; b < a && !raw_everywhere; b++)
-        if (dq.aggs[b].acc == ACC_HLL && dq.aggs[b].expr == PHIP_EXPR_COLUMN && ag.expr == PHIP_EXPR_COLUMN &&
-            dq.aggs[b].col_a == ag.column_a && dq.aggs[b].log2m != ag.log2m)
+        if (P.dq.aggs[b].acc == ACC_HLL && P.dq.aggs[b].expr == PHIP_EXPR_COLUMN && ag.expr == PHIP_EXPR_COLUMN &&
+            P.dq.aggs[b].col_a == ag.column_a && P.dq.aggs[b].log2m != ag.log2m)
           return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL of column %d with two log2m (%d, %d)", ag.column_a,
-                      dq.aggs[b].log2m, ag.log2m);
-      log2m = std::max(log2m, ag.log2m);
-      d.hll_slot = nhll++;
+                      P.dq.aggs[b].log2m, ag.log2m);
+      P.log2m = std::max(P.log2m, ag.log2m);
+      d.hll_slot = P.nhll++;
       d.log2m = ag.log2m;
     }
   }
-  dq.num_hll = nhll;
+  P.dq.num_hll = P.nhll;
   // Plain values of SUM / MIN / MAX (no filter leaf, group-by key or HLL reads the column) whose dictionary is
   // large read the segment's doc-order values: one load by doc instead of the doc's id bits plus a dependent
   // gather into a dictionary that does not stay in the XCD's L2 (~1M distinct prices per segment: random lines
   // from the Infinity Cache). The kernels take such a column as a raw one (DevCol.has_dict = 0).
-  std::vector<bool> use_vals(ncols, false);
-  const int64_t vals_min = materialize_min_dict();
-  const bool vpack_on = vpack_enabled();
+  use_vals.assign(ncols, false);
+  vals_min = materialize_min_dict();
+  vpack_on = vpack_enabled();
   {
-    const char *me = getenv("PHIP_MATERIALIZE");  // measurement override: "0" = ids + dictionary gathers
-    if (!(me && atoi(me) == 0) && !want_bitmap && vals_min >= 0) {
-      for (int a = 0; a < naggs; a++) {
+    // PHIP_MATERIALIZE (measurement override): "0" = ids + dictionary gathers
+    if (!env_off("PHIP_MATERIALIZE") && !P.want_bitmap && vals_min >= 0) {
+      for (int a = 0; a < P.naggs; a++) {
         const phip_aggregation &ag = q->aggregations[a];
         if (ag.function == PHIP_AGG_SUM || ag.function == PHIP_AGG_MIN || ag.function == PHIP_AGG_MAX) {
           use_vals[ag.column_a] = true;
           if (ag.expr != PHIP_EXPR_COLUMN) use_vals[ag.column_b] = true;
         }
       }
-      for (int a = 0; a < naggs; a++)
+      for (int a = 0; a < P.naggs; a++)
         if (q->aggregations[a].function == PHIP_AGG_HLL || is_distinct_fn(q->aggregations[a].function))
           use_vals[q->aggregations[a].column_a] = false;  // (their ids / per-id entries are read)
       for (int k = 0; k < q->num_group_by; k++)
         if (q->group_by_columns[k] >= 0 && q->group_by_columns[k] < ncols) use_vals[q->group_by_columns[k]] = false;
       if (q->filter_offsets && q->filter_nodes)
-        for (int i = q->filter_offsets[0]; i < q->filter_offsets[nprog * nseg]; i++) {
+        for (int i = q->filter_offsets[0]; i < q->filter_offsets[P.nprog * P.nseg]; i++) {
           const phip_filter_node &fn = q->filter_nodes[i];
           if (fn.op == PHIP_NODE_LEAF && fn.column >= 0 && fn.column < ncols) use_vals[fn.column] = false;
         }
@@ -3198,21 +3337,15 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     bool made = false;
     for (int c = 0; c < ncols; c++) {
       if (!use_vals[c]) continue;
-      for (int s = 0; s < nseg; s++) {
-        ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+      for (int s = 0; s < P.nseg; s++) {
+        ColumnStore &cs = segp[s]->cols[colidx[s][c]];
         if (!vals_eligible(cs, vals_min)) continue;
-        int32_t rc = ensure_vals(*segs[s], cs, st, &made, vpack_on);
+        int32_t rc = ensure_vals(*segp[s], cs, st, &made, vpack_on);
         if (rc) return rc;
       }
     }
     if (made) HIP_TRY(hipStreamSynchronize(st));
   }
-  // column c of segment s read as raw values (no dictionary, or its doc-order values above, packed or typed)
-  auto packed_vals = [&](const ColumnStore &cs) -> bool { return vpack_on && cs.vpack != nullptr; };
-  auto as_raw = [&](int s, int c) -> bool {
-    const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
-    return no_dict(cs) || (use_vals[c] && (packed_vals(cs) || cs.vals != nullptr) && vals_eligible(cs, vals_min));
-  };
   // Batched dense-tile walk (aggregate.hip agg_batch) only when every dictionary the aggregations
   // gather from is small enough to stay cache-resident. Gathers from a large dictionary (~1M distinct
   // prices per segment) are bound by random lines from the Infinity Cache, and more of them in flight
@@ -3220,42 +3353,39 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // 64-doc chunk vs 6.8 ms batched; over an 11-entry 4-bit column 1.33 ms vs 0.70 ms batched).
   {
     int64_t max_dict = 0;
-    for (int a = 0; a < naggs; a++) {
+    for (int a = 0; a < P.naggs; a++) {
       const phip_aggregation &ag = q->aggregations[a];
       if (ag.function == PHIP_AGG_COUNT) continue;
-      for (int s = 0; s < nseg; s++) {
+      for (int s = 0; s < P.nseg; s++) {
         for (int c : {ag.column_a, ag.expr != PHIP_EXPR_COLUMN ? ag.column_b : -1}) {
           if (c < 0) continue;
-          const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+          const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
           if (as_raw(s, c)) continue;
           const int64_t w = ag.function == PHIP_AGG_HLL ? 4 : ((cs.type == PHIP_TYPE_LONG || cs.type == PHIP_TYPE_DOUBLE) ? 8 : 4);
           max_dict = std::max<int64_t>(max_dict, (int64_t)cs.card * w);
         }
       }
     }
-    dq.dense_batch = max_dict <= (512 << 10) ? 1 : 0;
-    const char *db = getenv("PHIP_DENSE_BATCH");  // measurement override: "0" / "1"
-    if (db) dq.dense_batch = atoi(db) != 0;
-    dq.dense_min = kDenseMin;
-    const char *dm = getenv("PHIP_DENSE_MIN");  // measurement override
-    if (dm) dq.dense_min = std::max(1, atoi(dm));
+    P.dq.dense_batch = max_dict <= (512 << 10) ? 1 : 0;
+    P.dq.dense_batch = env_int("PHIP_DENSE_BATCH", P.dq.dense_batch) != 0;  // measurement override: "0" / "1"
+    P.dq.dense_min = std::max(1, env_int("PHIP_DENSE_MIN", kDenseMin));   // measurement override
     // Id histogram (agg_kernel kHist): SUM / MIN / MAX of one INT / LONG column whose dictionary has at most kHistCard
     // ids in every segment count the docs per id in LDS and fold count x value in at each segment's end -- the
     // per-doc dictionary gather goes (C4 SUM(M), 1000 ids). Integer sums stay exact (count x value wraps as the
     // repeated sum does); MIN / MAX do not depend on order. COUNTs beside them keep their own path.
-    dq.hist_aggs = 0;
-    dq.hist_col = -1;
-    dq.hist_words = 0;
+    P.dq.hist_aggs = 0;
+    P.dq.hist_col = -1;
+    P.dq.hist_words = 0;
     {
-      const char *he = getenv("PHIP_AGG_HIST");  // measurement override: "0" = gather the values
-      bool ok = q->num_group_by == 0 && dq.dense_batch && nhll == 0 && nprog == 1 && naggs <= 2 && !(he && atoi(he) == 0) &&
+      // PHIP_AGG_HIST (measurement override): "0" = gather the values
+      bool ok = q->num_group_by == 0 && P.dq.dense_batch && P.nhll == 0 && P.nprog == 1 && P.naggs <= 2 && !env_off("PHIP_AGG_HIST") &&
                 P.dist_agg.empty();
       int col = -1, max_card = 0;
       uint32_t mask = 0;
-      for (int a = 0; a < naggs && ok; a++) {
+      for (int a = 0; a < P.naggs && ok; a++) {
         const phip_aggregation &ag = q->aggregations[a];
-        if (dq.aggs[a].acc == ACC_COUNT) continue;
-        const int k = dq.aggs[a].acc;
+        if (P.dq.aggs[a].acc == ACC_COUNT) continue;
+        const int k = P.dq.aggs[a].acc;
         if ((k != ACC_SUM_I64 && k != ACC_MIN_F64 && k != ACC_MAX_F64) || ag.expr != PHIP_EXPR_COLUMN ||
             (col >= 0 && ag.column_a != col)) {
           ok = false;
@@ -3263,8 +3393,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         }
         col = ag.column_a;
         mask |= 1u << a;
-        for (int s = 0; s < nseg && ok; s++) {
-          const ColumnStore &cs = segs[s]->cols[colidx[s][col]];
+        for (int s = 0; s < P.nseg && ok; s++) {
+          const ColumnStore &cs = segp[s]->cols[colidx[s][col]];
           if (as_raw(s, col) || no_dict(cs) || (cs.type != PHIP_TYPE_INT && cs.type != PHIP_TYPE_LONG) ||
               cs.card < 1 || cs.card > kHistCard)
             ok = false;
@@ -3272,18 +3402,18 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         }
       }
       if (ok && mask) {
-        dq.hist_aggs = mask;
-        dq.hist_col = col;
-        dq.hist_words = (max_card + 1) / 2;
+        P.dq.hist_aggs = mask;
+        P.dq.hist_col = col;
+        P.dq.hist_words = (max_card + 1) / 2;
       }
     }
     // Stage the fixed-bit words of the gathered dictionary columns of a dense tile in LDS (one region
     // per distinct column, sized for its widest segment), when they fit kAggStageBudget per wave.
-    for (int a = 0; a < kMaxAggs; a++) dq.stage_slot_a[a] = dq.stage_slot_b[a] = -1;
+    for (int a = 0; a < kMaxAggs; a++) P.dq.stage_slot_a[a] = P.dq.stage_slot_b[a] = -1;
     std::vector<int> cols;
     std::vector<int> maxbits;
-    bool ok = dq.dense_batch != 0 && q->num_group_by == 0;
-    for (int a = 0; a < naggs && ok; a++) {
+    bool ok = P.dq.dense_batch != 0 && q->num_group_by == 0;
+    for (int a = 0; a < P.naggs && ok; a++) {
       const phip_aggregation &ag = q->aggregations[a];
       if (ag.function == PHIP_AGG_COUNT || is_distinct_fn(ag.function)) continue;  // (no value read in this walk)
       for (int which = 0; which < 2; which++) {
@@ -3291,8 +3421,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         if (c < 0) continue;
         int bits = 0;
         bool any_dict = false;
-        for (int s = 0; s < nseg; s++) {
-          const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+        for (int s = 0; s < P.nseg; s++) {
+          const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
           if (as_raw(s, c)) continue;
           any_dict = true;
           bits = std::max(bits, cs.bits);
@@ -3307,13 +3437,13 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
           cols.push_back(c);
           maxbits.push_back(bits);
         }
-        (which == 0 ? dq.stage_slot_a : dq.stage_slot_b)[a] = slot;
+        (which == 0 ? P.dq.stage_slot_a : P.dq.stage_slot_b)[a] = slot;
       }
     }
     int32_t off = 0;
     for (size_t k = 0; k < cols.size() && ok; k++) {
-      dq.stage_col[k] = cols[k];
-      dq.stage_off[k] = off + kStagePad;
+      P.dq.stage_col[k] = cols[k];
+      P.dq.stage_off[k] = off + kStagePad;
       off += 256 * maxbits[k] + 2 * kStagePad;
     }
     // dictionaries of at most kAggLdsDict bytes (in every segment) are read from LDS as well. (Round 6 measured 8 KiB
@@ -3321,49 +3451,53 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     // dictionary got slower at every selectivity -- 50 %: aggregation 1.33 -> 1.96 ms, 0.01 %: 0.16 -> 0.27 ms,
     // profiles/r06d_c4_lds_dict_ab.log -- the larger stage area halves the resident workgroups of a latency-bound walk)
     for (size_t k = 0; k < cols.size() && ok; k++) {
-      dq.stage_dict_off[k] = -1;
+      P.dq.stage_dict_off[k] = -1;
       int64_t bytes = 0;
       bool numeric = true;
-      for (int s = 0; s < nseg; s++) {
-        const ColumnStore &cs = segs[s]->cols[colidx[s][cols[k]]];
+      for (int s = 0; s < P.nseg; s++) {
+        const ColumnStore &cs = segp[s]->cols[colidx[s][cols[k]]];
         if (as_raw(s, cols[k])) continue;
         if (cs.type == PHIP_TYPE_STRING) numeric = false;
         const int64_t w = (cs.type == PHIP_TYPE_LONG || cs.type == PHIP_TYPE_DOUBLE) ? 8 : 4;
         bytes = std::max<int64_t>(bytes, (int64_t)cs.card * w);
       }
-      const char *ld = getenv("PHIP_AGG_LDS_DICT");  // measurement override: "0" keeps dictionaries in HBM
-      if (numeric && bytes <= kAggLdsDict && off + bytes <= kAggStageBudget && !(ld && atoi(ld) == 0)) {
-        dq.stage_dict_off[k] = off;
+      // PHIP_AGG_LDS_DICT (measurement override): "0" keeps dictionaries in HBM
+      if (numeric && bytes <= kAggLdsDict && off + bytes <= kAggStageBudget && !env_off("PHIP_AGG_LDS_DICT")) {
+        P.dq.stage_dict_off[k] = off;
         off += (int32_t)round_up(bytes, 16);
       }
     }
-    const char *ds = getenv("PHIP_AGG_STAGE");  // measurement override: "0" disables staging
-    if (ds && atoi(ds) == 0) ok = false;
+    if (env_off("PHIP_AGG_STAGE")) ok = false;  // measurement override: "0" disables staging
     if (ok && !cols.empty() && off <= kAggStageBudget) {
-      dq.num_stage = (int32_t)cols.size();
-      dq.stage_bytes = round_up(off, 16);
+      P.dq.num_stage = (int32_t)cols.size();
+      P.dq.stage_bytes = round_up(off, 16);
     } else {
-      dq.num_stage = 0;
-      dq.stage_bytes = 0;
-      for (int a = 0; a < kMaxAggs; a++) dq.stage_slot_a[a] = dq.stage_slot_b[a] = -1;
+      P.dq.num_stage = 0;
+      P.dq.stage_bytes = 0;
+      for (int a = 0; a < kMaxAggs; a++) P.dq.stage_slot_a[a] = P.dq.stage_slot_b[a] = -1;
     }
   }
+  return PHIP_OK;
+}
+
+// Selection (SelectionOnlyOperator): expressions, output kinds, query-global dictionaries of STRING columns; the
+// ORDER BY terms of a selection; the key digits and the regime of SELECT DISTINCT.
+int32_t PlanBuilder::plan_selection() {
   for (int k = 0; k < q->num_group_by; k++) {
     int c = q->group_by_columns[k];
     if (c < 0 || c >= ncols) return fail(PHIP_ERR_INVALID, "group-by column out of range");
     projected[c] = true;
-    proj_progs[c] |= (1u << nprog) - 1;  // every program's docs generate groups (FilteredGroupByOperator infos)
+    proj_progs[c] |= (1u << P.nprog) - 1;  // every program's docs generate groups (FilteredGroupByOperator infos)
   }
-  // selection (SelectionOnlyOperator): expressions, output kinds, query-global dictionaries of STRING columns
-  const int nsel = q->num_select;
-  if (nsel < 0 || nsel > kMaxSelect) return fail(PHIP_ERR_UNSUPPORTED, "selection: at most %d expressions", kMaxSelect);
-  if (nsel > 0 && (naggs > 0 || q->num_group_by > 0 || nprog > 1 || want_bitmap || !q->select))
+  P.nsel = q->num_select;
+  if (P.nsel < 0 || P.nsel > kMaxSelect) return fail(PHIP_ERR_UNSUPPORTED, "selection: at most %d expressions", kMaxSelect);
+  if (P.nsel > 0 && (P.naggs > 0 || q->num_group_by > 0 || P.nprog > 1 || P.want_bitmap || !q->select))
     return fail(PHIP_ERR_INVALID, "selection: no aggregations, group-by or filter programs beside the expressions");
-  DevSelQuery sq;
   memset(&sq, 0, sizeof(sq));
-  std::vector<int32_t> sel_types(nsel, 0);
-  std::vector<std::shared_ptr<Device::Remap>> sel_dicts(nsel), col_remap(ncols);
-  for (int k = 0; k < nsel; k++) {
+  P.sel_types.assign(P.nsel, 0);
+  P.sel_dicts.resize(P.nsel);
+  col_remap.resize(ncols);
+  for (int k = 0; k < P.nsel; k++) {
     const phip_select_expr &e = q->select[k];
     if (e.expr < PHIP_EXPR_COLUMN || e.expr > PHIP_EXPR_MUL || e.column_a < 0 || e.column_a >= ncols ||
         (e.expr != PHIP_EXPR_COLUMN && (e.column_b < 0 || e.column_b >= ncols)))
@@ -3375,63 +3509,60 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     for (int c : {e.column_a, e.expr != PHIP_EXPR_COLUMN ? e.column_b : -1}) {
       if (c < 0) continue;
       projected[c] = true;
-      const int t0 = segs[0]->cols[colidx[0][c]].type;
-      for (int s = 0; s < nseg; s++) {
-        const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+      const int t0 = segp[0]->cols[colidx[0][c]].type;
+      for (int s = 0; s < P.nseg; s++) {
+        const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
         if (cs.type != t0) return fail(PHIP_ERR_UNSUPPORTED, "selection: column %s changes type across segments", q->columns[c]);
         if (cs.fwd_kind == PHIP_FWD_HLL_REGISTERS)
           return fail(PHIP_ERR_INVALID, "selection of the HLL register column %s", q->columns[c]);
         if (cs.type == PHIP_TYPE_STRING && e.expr != PHIP_EXPR_COLUMN)
           return fail(PHIP_ERR_INVALID, "selection: numeric expression over STRING column %s", q->columns[c]);
         if (cs.type == PHIP_TYPE_STRING && (cs.fwd_kind == PHIP_FWD_RAW_CHUNK) !=
-                                               (segs[0]->cols[colidx[0][c]].fwd_kind == PHIP_FWD_RAW_CHUNK))
+                                               (segp[0]->cols[colidx[0][c]].fwd_kind == PHIP_FWD_RAW_CHUNK))
           return fail(PHIP_ERR_UNSUPPORTED, "selection: STRING column %s raw in some segments only", q->columns[c]);
       }
     }
-    const int t = segs[0]->cols[colidx[0][e.column_a]].type;
+    const int t = segp[0]->cols[colidx[0][e.column_a]].type;
     if (e.expr != PHIP_EXPR_COLUMN) {
       d.kind = SEL_F64;
-      sel_types[k] = PHIP_TYPE_DOUBLE;
-    } else if (t == PHIP_TYPE_STRING && segs[0]->cols[colidx[0][e.column_a]].fwd_kind == PHIP_FWD_RAW_CHUNK) {
+      P.sel_types[k] = PHIP_TYPE_DOUBLE;
+    } else if (t == PHIP_TYPE_STRING && segp[0]->cols[colidx[0][e.column_a]].fwd_kind == PHIP_FWD_RAW_CHUNK) {
       // a raw STRING column: the rows' locators, their bytes gathered after the rows are known (execute_select)
       d.kind = SEL_STR;
-      sel_types[k] = PHIP_TYPE_STRING;
+      P.sel_types[k] = PHIP_TYPE_STRING;
     } else if (t == PHIP_TYPE_STRING) {
       d.kind = SEL_ID;
-      sel_types[k] = PHIP_TYPE_STRING;
+      P.sel_types[k] = PHIP_TYPE_STRING;
       if (!col_remap[e.column_a]) {
-        std::vector<int> ci(nseg);
-        for (int s = 0; s < nseg; s++) ci[s] = colidx[s][e.column_a];
-        int32_t rc = build_remap(*dev, segs, ci, q->columns[e.column_a], col_remap[e.column_a]);
+        std::vector<int> ci(P.nseg);
+        for (int s = 0; s < P.nseg; s++) ci[s] = colidx[s][e.column_a];
+        int32_t rc = build_remap(*P.dev, segp, ci, q->columns[e.column_a], col_remap[e.column_a]);
         if (rc) return rc;
       }
-      sel_dicts[k] = col_remap[e.column_a];
+      P.sel_dicts[k] = col_remap[e.column_a];
     } else {
       d.kind = (t == PHIP_TYPE_INT || t == PHIP_TYPE_LONG) ? SEL_I64 : SEL_F64;
-      sel_types[k] = t;
+      P.sel_types[k] = t;
     }
   }
-  sq.num_select = nsel;
+  sq.num_select = P.nsel;
   sq.limit = std::max<int64_t>(0, q->select_limit);
   // selection ORDER BY (SelectionOrderByOperator): the terms over select[], the primary term's digit bound
   // (a distinct query's terms order its keys, below: the top-K machinery of a selection stays out of it)
-  const bool sel_distinct = q->select_distinct != 0;
-  const int nord = sel_distinct ? 0 : q->num_select_order;
-  DevSelOrder so;
+  P.sel_distinct = q->select_distinct != 0;
+  nord = P.sel_distinct ? 0 : q->num_select_order;
   memset(&so, 0, sizeof(so));
-  std::vector<SelOrderTerm> sel_terms;
-  int sel_order_cols = 0, sel_rest_cols = 0;
-  if (nord < 0 || (nord > 0 && (nsel == 0 || !q->select_order)))
+  if (nord < 0 || (nord > 0 && (P.nsel == 0 || !q->select_order)))
     return fail(PHIP_ERR_INVALID, "selection ORDER BY: terms without select expressions");
   if (nord > kMaxSelOrder) return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: at most %d terms", kMaxSelOrder);
   if (nord > 0) {
     if (!g_sel_order) return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: this library has no select_order kernels");
     if (q->select_keep <= 0) return fail(PHIP_ERR_INVALID, "selection ORDER BY: select_keep must be positive");
     std::vector<bool> in_order(ncols, false), in_rest(ncols, false);
-    std::vector<bool> is_term(nsel, false);
+    std::vector<bool> is_term(P.nsel, false);
     for (int j = 0; j < nord; j++) {
       const int k = q->select_order[j].select_index;
-      if (k < 0 || k >= nsel) return fail(PHIP_ERR_INVALID, "selection ORDER BY: term %d names no select expression", j);
+      if (k < 0 || k >= P.nsel) return fail(PHIP_ERR_INVALID, "selection ORDER BY: term %d names no select expression", j);
       const DevSelect &d = sq.sel[k];
       if (d.kind == SEL_STR)
         return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: raw STRING column %s as a term", q->columns[d.col_a]);
@@ -3439,29 +3570,29 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       t.sel = k;
       t.kind = d.kind;
       t.desc = q->select_order[j].descending ? 1 : 0;
-      t.card = d.kind == SEL_ID ? std::max<int64_t>(1, sel_dicts[k]->card) : 0;
+      t.card = d.kind == SEL_ID ? std::max<int64_t>(1, P.sel_dicts[k]->card) : 0;
       t.bits = 64;
       if (d.kind == SEL_ID) {
         // the query-global dictionary is in padded-byte order (compare_value): String.compareTo's only below U+E000
-        for (uint8_t b : sel_dicts[k]->values)
+        for (uint8_t b : P.sel_dicts[k]->values)
           if (b >= 0xEE)
             return fail(PHIP_ERR_UNSUPPORTED, "selection ORDER BY: STRING column %s holds a character at or above U+E000",
                         q->columns[d.col_a]);
         for (t.bits = 1; t.bits < 63 && ((int64_t)1 << t.bits) < t.card; t.bits++) {
         }
       }
-      sel_terms.push_back(t);
+      P.sel_terms.push_back(t);
       is_term[k] = true;
     }
-    for (int k = 0; k < nsel; k++)
+    for (int k = 0; k < P.nsel; k++)
       for (int c : {sq.sel[k].col_a, sq.sel[k].col_b}) (is_term[k] ? in_order : in_rest)[c] = true;
     for (int c = 0; c < ncols; c++) {
-      sel_order_cols += in_order[c] ? 1 : 0;
-      sel_rest_cols += in_rest[c] && !in_order[c] ? 1 : 0;
+      P.sel_order_cols += in_order[c] ? 1 : 0;
+      P.sel_rest_cols += in_rest[c] && !in_order[c] ? 1 : 0;
     }
     // the primary term's images lie in [lo, hi]: ids by the cardinality, INT / LONG by the segments' value ranges,
     // dictionary FLOAT / DOUBLE by the dictionaries' ends, else every image (a digit outside the bound clamps)
-    const SelOrderTerm &t0 = sel_terms[0];
+    const SelOrderTerm &t0 = P.sel_terms[0];
     const DevSelect &d0 = sq.sel[t0.sel];
     const uint64_t sign = 0x8000000000000000ull;
     auto dbl_image = [](double v) -> uint64_t {  // dev_common.h double_order
@@ -3476,8 +3607,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     } else if (d0.expr == PHIP_EXPR_COLUMN) {
       bool known = true;
       uint64_t l = ~0ull, h = 0;
-      for (int s = 0; s < nseg && known; s++) {
-        const ColumnStore &cs = segs[s]->cols[colidx[s][d0.col_a]];
+      for (int s = 0; s < P.nseg && known; s++) {
+        const ColumnStore &cs = segp[s]->cols[colidx[s][d0.col_a]];
         if (d0.kind == SEL_I64 && cs.has_range) {
           l = std::min(l, (uint64_t)cs.vmin ^ sign);
           h = std::max(h, (uint64_t)cs.vmax ^ sign);
@@ -3517,52 +3648,49 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     so.imin = lo;
     for (so.shift = 0; ((hi - lo) >> so.shift) >= (uint64_t)kSelOrderBins; so.shift++) {
     }
-    const char *pr = getenv("PHIP_SELECT_ORDER_PRUNE");  // measurement: 0 = every matched doc is a candidate
-    so.prune = pr && atoi(pr) == 0 ? 0 : 1;
+    so.prune = env_off("PHIP_SELECT_ORDER_PRUNE") ? 0 : 1;  // measurement: 0 = every matched doc is a candidate
     so.keep = q->select_keep;
     sq.limit = INT64_MAX;  // the ranks are those of all matched docs
   }
   // SELECT DISTINCT (DistinctOperator with the dictionary-based executors): the columns' digits, most significant
   // first -- the ORDER BY terms in their order, then the remaining columns in select order -- and the regime the key
   // space admits (distinct_rows.hip)
-  DevDistinctRows drq;
-  DistinctRowsDecode drd;
-  memset(&drq, 0, sizeof(drq));
-  memset(&drd, 0, sizeof(drd));
-  std::vector<std::vector<uint64_t>> dr_values(sel_distinct ? nsel : 0);  // per SELECT column: the dictionary as slots
-  if (sel_distinct) {
+  memset(&P.drq, 0, sizeof(P.drq));
+  memset(&P.dr_decode, 0, sizeof(P.dr_decode));
+  dr_values.resize(P.sel_distinct ? P.nsel : 0);
+  if (P.sel_distinct) {
     if (!g_distinct_rows) return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: this library has no distinct_rows kernels");
-    if (nsel == 0) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: no columns");
-    if (nsel > kMaxDistinctRowCols)
-      return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: %d columns, at most %d", nsel, kMaxDistinctRowCols);
+    if (P.nsel == 0) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: no columns");
+    if (P.nsel > kMaxDistinctRowCols)
+      return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: %d columns, at most %d", P.nsel, kMaxDistinctRowCols);
     const int nterm = q->num_select_order;
-    if (nterm < 0 || nterm > nsel || (nterm > 0 && !q->select_order))
+    if (nterm < 0 || nterm > P.nsel || (nterm > 0 && !q->select_order))
       return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: malformed ORDER BY terms");
     if (q->select_keep <= 0) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: select_keep must be positive");
-    for (int k = 0; k < nsel; k++) {
+    for (int k = 0; k < P.nsel; k++) {
       const int c = q->select[k].column_a;
       if (q->select[k].expr != PHIP_EXPR_COLUMN)
         return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: expression %d is not a column", k);
       for (int k2 = 0; k2 < k; k2++)
         if (q->select[k2].column_a == c) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: column %s twice", q->columns[c]);
-      for (int s = 0; s < nseg; s++) {
-        const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+      for (int s = 0; s < P.nseg; s++) {
+        const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
         if (no_dict(cs)) return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: raw (no-dictionary) column %s", q->columns[c]);
         if (cs.fwd_kind == PHIP_FWD_FIXED_BIT_MV)
           return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: multi-value column %s", q->columns[c]);
       }
       if (!col_remap[c]) {
-        std::vector<int> ci(nseg);
-        for (int s = 0; s < nseg; s++) ci[s] = colidx[s][c];
-        int32_t rc = build_remap(*dev, segs, ci, q->columns[c], col_remap[c]);
+        std::vector<int> ci(P.nseg);
+        for (int s = 0; s < P.nseg; s++) ci[s] = colidx[s][c];
+        int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], col_remap[c]);
         if (rc) return rc;
       }
     }
     std::vector<int> order;  // select indexes, most significant digit first
-    std::vector<int> desc(nsel, 0);
+    std::vector<int> desc(P.nsel, 0);
     for (int j = 0; j < nterm; j++) {
       const int k = q->select_order[j].select_index;
-      if (k < 0 || k >= nsel) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: ORDER BY term %d names no column", j);
+      if (k < 0 || k >= P.nsel) return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: ORDER BY term %d names no column", j);
       if (std::find(order.begin(), order.end(), k) != order.end())
         return fail(PHIP_ERR_INVALID, "SELECT DISTINCT: ORDER BY names column %d twice", k);
       const Device::Remap &r = *col_remap[q->select[k].column_a];
@@ -3574,36 +3702,34 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       order.push_back(k);
       desc[k] = q->select_order[j].descending ? 1 : 0;
     }
-    for (int k = 0; k < nsel; k++)
+    for (int k = 0; k < P.nsel; k++)
       if (std::find(order.begin(), order.end(), k) == order.end()) order.push_back(k);
     long double space = 1;
-    for (int k = 0; k < nsel; k++) space *= (long double)std::max(col_remap[q->select[k].column_a]->card, 1);
+    for (int k = 0; k < P.nsel; k++) space *= (long double)std::max(col_remap[q->select[k].column_a]->card, 1);
     if (space >= 9223372036854775808.0L)
       return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: a key space of %.3Lg rows, the limit is 2^63", space);
     uint64_t stride = 1;
-    drq.num_cols = drd.num_cols = nsel;
-    for (int j = nsel - 1; j >= 0; j--) {
+    P.drq.num_cols = P.dr_decode.num_cols = P.nsel;
+    for (int j = P.nsel - 1; j >= 0; j--) {
       const int k = order[j];
       const int32_t card = std::max(col_remap[q->select[k].column_a]->card, 1);
-      drq.col[j] = q->select[k].column_a;
-      drq.card[j] = drd.card[k] = card;
-      drq.desc[j] = drd.desc[k] = desc[k];
-      drq.stride[j] = drd.stride[k] = stride;
+      P.drq.col[j] = q->select[k].column_a;
+      P.drq.card[j] = P.dr_decode.card[k] = card;
+      P.drq.desc[j] = P.dr_decode.desc[k] = desc[k];
+      P.drq.stride[j] = P.dr_decode.stride[k] = stride;
       stride *= (uint64_t)card;
     }
-    drq.key_space = (int64_t)stride;
-    drq.num_words = (int64_t)((stride + 31) / 32);
+    P.drq.key_space = (int64_t)stride;
+    P.drq.num_words = (int64_t)((stride + 31) / 32);
     // the regime: the bitmap's words within the LDS budget (PHIP_AGG_DISTINCT's, with its clamp), else its bytes within
     // PHIP_DISTINCT_ROWS_MAX_BYTES, else sorted keys (their budget is checked once the work list is known)
-    const char *lw = getenv("PHIP_DISTINCT_LDS_WORDS");
-    const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(lw ? atoll(lw) : kDistinctLdsWords, 12288));
-    const char *mb = getenv("PHIP_DISTINCT_ROWS_MAX_BYTES");
-    const int64_t max_bytes = mb ? atoll(mb) : (int64_t)256 << 20;
-    drq.regime = drq.num_words <= lds_words ? DR_LDS : (drq.num_words <= max_bytes / 4 ? DR_GLOBAL : DR_SORTED);
+    const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(env_i64("PHIP_DISTINCT_LDS_WORDS", kDistinctLdsWords), 12288));
+    const int64_t max_bytes = env_i64("PHIP_DISTINCT_ROWS_MAX_BYTES", (int64_t)256 << 20);
+    P.drq.regime = P.drq.num_words <= lds_words ? DR_LDS : (P.drq.num_words <= max_bytes / 4 ? DR_GLOBAL : DR_SORTED);
     // key -> row: every column's query-global dictionary as 8-byte result slots (STRING: the id is the slot)
-    for (int k = 0; k < nsel; k++) {
+    for (int k = 0; k < P.nsel; k++) {
       const Device::Remap &r = *col_remap[q->select[k].column_a];
-      sel_dicts[k] = col_remap[q->select[k].column_a];
+      P.sel_dicts[k] = col_remap[q->select[k].column_a];
       if (r.type == PHIP_TYPE_STRING) continue;
       const int w = type_width(r.type);
       if (r.raw || r.values.size() != (size_t)r.card * w)
@@ -3629,7 +3755,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     }
     sq.limit = INT64_MAX;  // (DR_SORTED: the ranks are those of all matched docs)
   }
-  int num_projected = 0;
+  return PHIP_OK;
+}
+
+// The projections the statistics count, the group-by key space and its table's placement (dense / hash), and the
+// descriptor of the exact DISTINCTCOUNT / value-count pass.
+int32_t PlanBuilder::plan_group_table() {
   {
     std::vector<bool> counted = projected;  // (tuple keys: the query's own group-by columns are the projected ones)
     if (P.tuple_keys)
@@ -3640,12 +3771,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       counted[nreal + j] = false;
       for (int c : derived_inputs[j]) counted[c] = true;
     }
-    for (bool p : counted) num_projected += p ? 1 : 0;
+    for (bool p : counted) P.num_projected += p ? 1 : 0;
   }
   // ... and per filter program (several programs: each info's own projection): the distinct columns its functions
   // read, a derived column standing for its program's columns
-  std::vector<int> prog_projected(nprog, 0);
-  for (int p = 0; p < nprog; p++) {
+  P.prog_projected.assign(P.nprog, 0);
+  for (int p = 0; p < P.nprog; p++) {
     std::vector<bool> counted(ncols, false);
     for (int c = 0; c < ncols; c++) {
       if (!projected[c] || !((proj_progs[c] >> p) & 1u)) continue;
@@ -3653,40 +3784,37 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       else
         for (int i : derived_inputs[c - nreal]) counted[i] = true;
     }
-    for (bool b : counted) prog_projected[p] += b ? 1 : 0;
+    for (bool b : counted) P.prog_projected[p] += b ? 1 : 0;
   }
 
   // group-by key space
-  const bool group_by = q->num_group_by > 0;
-  int64_t gb_key_space = 0;
-  bool gb_force_hash = false;
-  std::vector<std::shared_ptr<Device::Remap>> gb_dicts;
-  std::vector<std::vector<int32_t *>> gb_remap_dev;  // [k][seg]
-  if (group_by) {
-    dq.num_group_by = q->num_group_by;
-    dq.own_count_rows = nprog > 1 ? 1 : 0;
+  P.group_by = q->num_group_by > 0;
+  P.num_group_by = q->num_group_by;
+  if (P.group_by) {
+    P.dq.num_group_by = q->num_group_by;
+    P.dq.own_count_rows = P.nprog > 1 ? 1 : 0;
     int64_t stride = 1;
     for (int k = 0; k < q->num_group_by; k++) {
       int c = q->group_by_columns[k];
-      std::vector<int> ci(nseg);
-      for (int s = 0; s < nseg; s++) ci[s] = colidx[s][c];
+      std::vector<int> ci(P.nseg);
+      for (int s = 0; s < P.nseg; s++) ci[s] = colidx[s][c];
       // the null key (phip_query_desc.null_group_by): one more id, after the dictionary's, when some segment's
       // column holds a null doc
       bool null_key = false;
       if ((q->null_group_by >> k) & 1)
-        for (int s = 0; s < nseg; s++) null_key |= segs[s]->cols[ci[s]].nulls != nullptr;
+        for (int s = 0; s < P.nseg; s++) null_key |= segp[s]->cols[ci[s]].nulls != nullptr;
       std::shared_ptr<Device::Remap> r;
       if (P.tuple_keys) {
         r = P.tuple_remap;
       } else {
-        int32_t rc = build_remap(*dev, segs, ci, q->columns[c], r, null_key);
+        int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], r, null_key);
         if (rc) return rc;
       }
-      gb_dicts.push_back(r);
+      P.gb_dicts.push_back(r);
       const int64_t radix = (int64_t)r->card + (null_key ? 1 : 0);
       P.gb_radix.push_back(radix);
-      dq.gb_cols[k] = c;
-      dq.gb_stride[k] = stride;
+      P.dq.gb_cols[k] = c;
+      P.dq.gb_stride[k] = stride;
       if ((double)stride * (double)radix > (double)((int64_t)1 << 62))
         return fail(PHIP_ERR_UNSUPPORTED, "group-by key space exceeds 2^62");
       stride *= radix;
@@ -3696,659 +3824,634 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     // role, DictionaryBasedGroupKeyGenerator.java:105-186): capacity = the next power of two >= 2x the
     // number of groups possible (min of key space and docs), so probe sequences stay short.
     int64_t docs = 0;
-    for (int s = 0; s < nseg; s++) docs += segs[s]->num_docs;
+    for (int s = 0; s < P.nseg; s++) docs += segp[s]->num_docs;
     if (tl_node_docs > 0) docs = tl_node_docs;  // a node plan's part: the node's docs bound the groups
-    const char *hm = getenv("PHIP_GB_HASH");  // measurement override: "1" forces the hash table
-    const bool force_hash = hm && atoi(hm) != 0;
     gb_key_space = stride;
-    gb_force_hash = force_hash;
-    if (force_hash || stride > ((int64_t)1 << 26) || (stride > ((int64_t)1 << 22) && stride > 4 * docs)) {
+    gb_force_hash = env_int("PHIP_GB_HASH", 0) != 0;  // measurement override: "1" forces the hash table
+    if (gb_force_hash || stride > ((int64_t)1 << 26) || (stride > ((int64_t)1 << 22) && stride > 4 * docs)) {
       const int64_t bound = std::max<int64_t>(1, std::min<int64_t>(stride, docs));
       int64_t cap = 1024;
       while (cap < 2 * bound) cap <<= 1;
       if (const char *hc = getenv("PHIP_GB_HASH_CAP"))  // test override: a smaller table, so it must grow and rerun
         cap = std::max<int64_t>(64, std::min<int64_t>(cap, (int64_t)1 << (63 - __builtin_clzll((uint64_t)std::max(2LL, atoll(hc))))));
-      const int64_t per_slot = 8 + 8 * (1 + (int64_t)naggs);
+      const int64_t per_slot = 8 + 8 * (1 + (int64_t)P.naggs);
       if (cap * per_slot > ((int64_t)24 << 30))
         return fail(PHIP_ERR_UNSUPPORTED, "group-by hash table of %lld slots exceeds the memory budget", (long long)cap);
-      dq.num_groups = cap;
-      dq.mode = GB_HASH;
+      P.dq.num_groups = cap;
+      P.dq.mode = GB_HASH;
     } else {
-      dq.num_groups = stride;
+      P.dq.num_groups = stride;
     }
   }
 
   // exact DISTINCTCOUNT (distinct.hip): one bitmap row per dense group key, one run of words per slot over the
   // column's query-global dictionary (the per-segment id remap the group-by columns use)
-  DevDistinctQuery dstq;
-  memset(&dstq, 0, sizeof(dstq));
-  if (!P.dist_agg.empty()) {
+  memset(&P.dstq, 0, sizeof(P.dstq));
+  P.ndist = (int)P.dist_agg.size();
+  if (P.ndist > 0) {
     bool any_counts = false;
     for (int a : P.dist_agg) any_counts |= q->aggregations[a].function == PHIP_AGG_VALUE_COUNTS;
     const char *dn = any_counts ? "DISTINCTCOUNT / value counts" : "DISTINCTCOUNT";
-    if (group_by && dq.mode == GB_HASH)
+    if (P.group_by && P.dq.mode == GB_HASH)
       return fail(PHIP_ERR_UNSUPPORTED, "%s over a hash-table group-by key space", dn);
-    for (const auto &gd : gb_dicts)
+    for (const auto &gd : P.gb_dicts)
       if (gd->raw || !gd->ids.empty()) return fail(PHIP_ERR_UNSUPPORTED, "%s over raw group-by keys", dn);
-    dstq.num_slots = (int32_t)P.dist_agg.size();
-    dstq.num_rows = group_by ? dq.num_groups : 1;
-    dstq.num_group_by = q->num_group_by;
+    P.dstq.num_slots = (int32_t)P.dist_agg.size();
+    P.dstq.num_rows = P.group_by ? P.dq.num_groups : 1;
+    P.dstq.num_group_by = q->num_group_by;
     for (int k = 0; k < q->num_group_by; k++) {
-      dstq.gb_cols[k] = dq.gb_cols[k];
-      dstq.gb_stride[k] = dq.gb_stride[k];
+      P.dstq.gb_cols[k] = P.dq.gb_cols[k];
+      P.dstq.gb_stride[k] = P.dq.gb_stride[k];
     }
     int64_t words = 0;
-    for (int s2 = 0; s2 < dstq.num_slots; s2++) {
+    for (int s2 = 0; s2 < P.dstq.num_slots; s2++) {
       const int c = q->aggregations[P.dist_agg[s2]].column_a;
       if (!col_remap[c]) {
-        std::vector<int> ci(nseg);
-        for (int s = 0; s < nseg; s++) ci[s] = colidx[s][c];
-        int32_t rc = build_remap(*dev, segs, ci, q->columns[c], col_remap[c]);
+        std::vector<int> ci(P.nseg);
+        for (int s = 0; s < P.nseg; s++) ci[s] = colidx[s][c];
+        int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], col_remap[c]);
         if (rc) return rc;
       }
       P.dist_dicts.push_back(col_remap[c]);
       const bool counts = q->aggregations[P.dist_agg[s2]].function == PHIP_AGG_VALUE_COUNTS;
       P.dist_kinds.push_back(counts ? PHIP_DISTINCT_SLOT_COUNTS : PHIP_DISTINCT_SLOT_BITS);
-      dstq.slot_col[s2] = c;
-      dstq.slot_card[s2] = col_remap[c]->card;
-      dstq.slot_kind[s2] = P.dist_kinds.back();
-      dstq.slot_off[s2] = words;
+      P.dstq.slot_col[s2] = c;
+      P.dstq.slot_card[s2] = col_remap[c]->card;
+      P.dstq.slot_kind[s2] = P.dist_kinds.back();
+      P.dstq.slot_off[s2] = words;
       // a bit per query-global id, or a u32 count per id
       words += counts ? std::max(col_remap[c]->card, 0) : ceil_div(std::max(col_remap[c]->card, 0), 32);
     }
-    dstq.row_words = words;
-    const char *mb = getenv("PHIP_DISTINCT_MAX_BYTES");
-    const int64_t max_bytes = mb ? atoll(mb) : (int64_t)256 << 20;
-    if ((long double)dstq.num_rows * (long double)words * 4 > (long double)max_bytes)
+    P.dstq.row_words = words;
+    const int64_t max_bytes = env_i64("PHIP_DISTINCT_MAX_BYTES", (int64_t)256 << 20);
+    if ((long double)P.dstq.num_rows * (long double)words * 4 > (long double)max_bytes)
       return fail(PHIP_ERR_UNSUPPORTED, "%s: %lld rows x %lld words exceed PHIP_DISTINCT_MAX_BYTES %lld", dn,
-                  (long long)dstq.num_rows, (long long)words, (long long)max_bytes);
+                  (long long)P.dstq.num_rows, (long long)words, (long long)max_bytes);
     // LDS regime: no group-by and every slot's words within the budget (default kDistinctLdsWords = 32 KiB per
     // workgroup: four workgroups stay resident per CU, and a flush is at most 8192 atomics per workgroup); clamped to
     // 48 KiB, below the 64 KiB a launch may ask for
-    const char *lw = getenv("PHIP_DISTINCT_LDS_WORDS");
-    const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(lw ? atoll(lw) : kDistinctLdsWords, 12288));
-    dstq.lds = (!group_by && words <= lds_words) ? 1 : 0;
+    const int64_t lds_words = std::max<int64_t>(0, std::min<int64_t>(env_i64("PHIP_DISTINCT_LDS_WORDS", kDistinctLdsWords), 12288));
+    P.dstq.lds = (!P.group_by && words <= lds_words) ? 1 : 0;
     // counts slots of a small dictionary in global rows: the lanes of a wave that share a word add once (distinct.hip).
     // PHIP_COUNTS_COMBINE_CARD / PHIP_COUNTS_COMBINE_ROUNDS (environment, measurement overrides: tools/percentile_probe.py)
     // = the largest such cardinality (0 = never) and the rounds of peeling
-    const char *cc = getenv("PHIP_COUNTS_COMBINE_CARD"), *cr = getenv("PHIP_COUNTS_COMBINE_ROUNDS");
-    dstq.combine_rounds = (int32_t)std::max<int64_t>(0, std::min<int64_t>(cr ? atoll(cr) : kCountsCombineRounds, 64));
-    dstq.combine_card = (int32_t)std::max<int64_t>(0, std::min<int64_t>(cc ? atoll(cc) : kCountsCombineCard, INT32_MAX));
+    P.dstq.combine_rounds = (int32_t)std::max<int64_t>(0, std::min<int64_t>(env_i64("PHIP_COUNTS_COMBINE_ROUNDS", kCountsCombineRounds), 64));
+    P.dstq.combine_card = (int32_t)std::max<int64_t>(0, std::min<int64_t>(env_i64("PHIP_COUNTS_COMBINE_CARD", kCountsCombineCard), INT32_MAX));
   }
+  return PHIP_OK;
+}
 
-  // ---- staging blob: segments, nodes, leaf aux ------------------------------------------------
-  Blob blob;
-  std::vector<DevNode> nodes;
-  std::vector<AuxFix> aux_fix;  // node.aux = dev_base + off
-  struct InvLeaf {
-    size_t node;
-    int seg;
-    int col;
-    const phip_filter_node *src;
-    int entry;  // (segment, program) entry whose program holds the leaf
-    int slot;   // index among that entry's inverted leaves
-    // a range / set leaf over a multi-value column: its doc words come from mv_scan_kernel, not from bitmaps
-    bool mv = false;
-    int32_t mv_lo = 0, mv_hi = 0, mv_invert = 0, mv_set_words = 0;
-    size_t mv_set_off = 0;  // the id bitmap in the blob (mv_set_words > 0)
-    bool mv_stats = false;  // the leaf's program counts in numEntriesScannedInFilter
-    // a RAW_STRING_MATCH leaf: its doc words come from strmatch_kernel (mv_invert / mv_stats as for an MV leaf)
-    bool sm = false;
-    size_t sm_table_off = 0;  // the table image in the blob
-    int32_t sm_table_words = 0, sm_states = 0, sm_classes = 0, sm_start = 0, sm_absorb_end = 0, sm_accept_begin = 0,
-            sm_accept_end = 0;
-  };
-  std::vector<bool> entry_has_work;  // per (segment, program) entry
-  std::vector<InvLeaf> inv_leaves;
-  int num_entries = 0;  // (segment, program) entries, pruned ones included
-  int64_t total_work = 0;
-  int64_t total_docs = 0;
-  std::vector<DevSeg> dsegs;  // (segment, program) entries with work only, segment-major
-  dsegs.reserve((size_t)nseg * nprog);
-  bool hll_made = false;
-  std::vector<bool> hll_doc_used((size_t)nseg * ncols, false);  // (segment, column): HLL entries read by doc
-  std::vector<bool> hll_doc16_used((size_t)nseg * ncols, false);  // ... 16-bit ones
+// The staging blob's segments, nodes and leaf aux: one DevSeg per (segment, program) entry with work (segment-major,
+// a segment's programs adjacent, so they read its columns back to back), its filter program lowered to postfix nodes.
+int32_t PlanBuilder::stage_segments() {
+  P.dsegs.reserve((size_t)P.nseg * P.nprog);
+  hll_doc_used.assign((size_t)P.nseg * ncols, false);
+  hll_doc16_used.assign((size_t)P.nseg * ncols, false);
   // group-by records (build_records): dense key spaces of dictionary keys, for every group-by the aggregation kernel
   // walks (PHIP_GB_RECORD=0: the columns' own layouts; =1: a record for any number of fields, else from kRecMinFields)
-  const char *gre = getenv("PHIP_GB_RECORD");
-  const bool rec_want = group_by && dq.mode != GB_HASH && gb_key_space <= ((int64_t)1 << 22) && !want_bitmap &&
-                        q->num_group_by <= kRecKeys && !(gre && atoi(gre) == 0);
-  const int rec_min_fields = gre && atoi(gre) == 1 ? 1 : kRecMinFields;
-  for (int a = 0; a < kMaxAggs; a++) dq.rec_fa[a] = dq.rec_fb[a] = -1;
-  const char *hde = getenv("PHIP_HLL_DOC");  // measurement override: "0" = gather the per-id table
-  const char *mze = getenv("PHIP_MATERIALIZE");
-  const bool hll_doc_on = !(hde && atoi(hde) == 0) && !(mze && atoi(mze) == 0) && !want_bitmap;
-  for (int s = 0; s < nseg; s++) {
-    Segment &sg = *segs[s];
-    total_docs += sg.num_docs;
+  rec_want = P.group_by && P.dq.mode != GB_HASH && gb_key_space <= ((int64_t)1 << 22) && !P.want_bitmap &&
+             q->num_group_by <= kRecKeys && !env_off("PHIP_GB_RECORD");
+  rec_min_fields = env_int("PHIP_GB_RECORD", 0) == 1 ? 1 : kRecMinFields;
+  for (int a = 0; a < kMaxAggs; a++) P.dq.rec_fa[a] = P.dq.rec_fb[a] = -1;
+  // PHIP_HLL_DOC (measurement override): "0" = gather the per-id table
+  hll_doc_on = !env_off("PHIP_HLL_DOC") && !env_off("PHIP_MATERIALIZE") && !P.want_bitmap;
+  for (int s = 0; s < P.nseg; s++) {
+    P.total_docs += segp[s]->num_docs;
     DevSeg seg_ds;
     memset(&seg_ds, 0, sizeof(seg_ds));
-    DevSeg &ds = seg_ds;
-    ds.num_docs = sg.num_docs;
-    ds.seg_index = s;
-    for (int c = 0; c < ncols; c++) {
-      ColumnStore &cs = sg.cols[colidx[s][c]];
-      DevCol &dc = ds.cols[c];
-      dc.words = cs.words;
-      dc.dict = cs.dict;
-      dc.raw = cs.raw;
-      dc.bits = cs.bits;
-      dc.card = cs.card;
-      dc.type = cs.type;
-      dc.has_dict = !no_dict(cs);
-      if (dc.has_dict && as_raw(s, c)) {  // doc-order values of a value-only column
-        dc.has_dict = 0;
-        if (packed_vals(cs)) {
-          dc.raw = nullptr;
-          dc.vpack = cs.vpack;
-          dc.vbase = cs.vmin;
-          dc.vbits = cs.vbits;
-        } else {
-          dc.raw = cs.vals;
-        }
-      }
-      dc.hll_rows = cs.hll_log2m;
-      dc.str_off = cs.str_off;
-      dc.planes = cs.planes;
-      dc.lds_off = -1;
-    }
-    for (int a = 0; a < naggs; a++) {
-      if (dq.aggs[a].acc != ACC_HLL || dq.aggs[a].expr != PHIP_EXPR_COLUMN) continue;  // (an expression: hashed per doc)
-      ColumnStore &cs = sg.cols[colidx[s][dq.aggs[a].col_a]];
-      if (cs.fwd_kind == PHIP_FWD_HLL_REGISTERS) continue;  // the register rows are the column's raw values
-      if (no_dict(cs)) continue;  // raw values: hashed per doc on the device
-      uint32_t *h;
-      int32_t rc = ensure_hll(cs, dq.aggs[a].log2m, &h);
-      if (rc) return rc;
-      ds.cols[dq.aggs[a].col_a].hll = h;
-      if (hll_doc_on && cs.words != nullptr && (int64_t)cs.card * 4 >= vals_min && vals_min >= 0) {
-        // 16-bit entries where log2m <= 11 (PHIP_HLL_DOC16=0: the 32-bit ones, A/B)
-        const char *h16 = getenv("PHIP_HLL_DOC16");
-        const bool doc16 = !(h16 && atoi(h16) == 0);
-        if (doc16 && dq.aggs[a].log2m <= 11) {
-          uint16_t *hd;
-          rc = ensure_hll_doc16(sg, cs, dq.aggs[a].log2m, h, st, &hll_made, &hd);
-          if (rc) return rc;
-          ds.cols[dq.aggs[a].col_a].hll_doc16 = hd;
-          hll_doc16_used[(size_t)s * ncols + dq.aggs[a].col_a] = true;
-        } else {
-          uint32_t *hd;
-          rc = ensure_hll_doc(sg, cs, dq.aggs[a].log2m, h, st, &hll_made, &hd);
-          if (rc) return rc;
-          ds.cols[dq.aggs[a].col_a].hll_doc = hd;
-        }
-        hll_doc_used[(size_t)s * ncols + dq.aggs[a].col_a] = true;
+    seg_ds.num_docs = segp[s]->num_docs;
+    seg_ds.seg_index = s;
+    int32_t rc = stage_columns(s, seg_ds);
+    if (rc) return rc;
+    if (segp[s]->num_docs == 0) continue;
+    for (int prog = 0; prog < P.nprog; prog++)
+      if ((rc = lower_filter_program(s, prog, seg_ds))) return rc;
+  }
+  if (hll_made) HIP_TRY(hipStreamSynchronize(st));
+  if (P.total_work > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many tiles in one query");
+  P.dq.total_work = (int32_t)P.total_work;
+  int32_t rc = size_hash_table();
+  if (rc) return rc;
+  P.dq.num_segs = (int32_t)P.dsegs.size();
+  segs_off = blob.reserve(sizeof(DevSeg) * std::max<size_t>(P.dsegs.size(), 1));
+  return PHIP_OK;
+}
+
+// One segment's DevSeg, shared by its programs' entries: the columns as the kernels read them, the HLL entry tables
+// (per id, and per doc where that pays), the group-by ids.
+int32_t PlanBuilder::stage_columns(int s, DevSeg &ds) {
+  Segment &sg = *segp[s];
+  for (int c = 0; c < ncols; c++) {
+    ColumnStore &cs = sg.cols[colidx[s][c]];
+    DevCol &dc = ds.cols[c];
+    dc.words = cs.words;
+    dc.dict = cs.dict;
+    dc.raw = cs.raw;
+    dc.bits = cs.bits;
+    dc.card = cs.card;
+    dc.type = cs.type;
+    dc.has_dict = !no_dict(cs);
+    if (dc.has_dict && as_raw(s, c)) {  // doc-order values of a value-only column
+      dc.has_dict = 0;
+      if (packed_vals(cs)) {
+        dc.raw = nullptr;
+        dc.vpack = cs.vpack;
+        dc.vbase = cs.vmin;
+        dc.vbits = cs.vbits;
+      } else {
+        dc.raw = cs.vals;
       }
     }
-    for (int k = 0; k < q->num_group_by; k++) {
-      DevCol &gc = ds.cols[q->group_by_columns[k]];
-      gc.remap = gb_dicts[k]->dev[s];
-      if (gb_dicts[k]->raw) gc.gb_base = gb_dicts[k]->raw_base;
-      if (!gb_dicts[k]->ids.empty()) gc.gb_ids = gb_dicts[k]->ids[s];  // a raw FLOAT / DOUBLE key: its id column
-      if (P.gb_radix[k] > gb_dicts[k]->card) {  // a null-key column: its null docs (if this segment has any)
-        gc.gb_nulls = segs[s]->cols[colidx[s][q->group_by_columns[k]]].nulls;
-        gc.gb_null_id = gb_dicts[k]->card;
+    dc.hll_rows = cs.hll_log2m;
+    dc.str_off = cs.str_off;
+    dc.planes = cs.planes;
+    dc.lds_off = -1;
+  }
+  for (int a = 0; a < P.naggs; a++) {
+    if (P.dq.aggs[a].acc != ACC_HLL || P.dq.aggs[a].expr != PHIP_EXPR_COLUMN) continue;  // (an expression: hashed per doc)
+    ColumnStore &cs = sg.cols[colidx[s][P.dq.aggs[a].col_a]];
+    if (cs.fwd_kind == PHIP_FWD_HLL_REGISTERS) continue;  // the register rows are the column's raw values
+    if (no_dict(cs)) continue;  // raw values: hashed per doc on the device
+    uint32_t *h;
+    int32_t rc = ensure_hll(cs, P.dq.aggs[a].log2m, &h);
+    if (rc) return rc;
+    ds.cols[P.dq.aggs[a].col_a].hll = h;
+    if (hll_doc_on && cs.words != nullptr && (int64_t)cs.card * 4 >= vals_min && vals_min >= 0) {
+      // 16-bit entries where log2m <= 11 (PHIP_HLL_DOC16=0: the 32-bit ones, A/B)
+      if (!env_off("PHIP_HLL_DOC16") && P.dq.aggs[a].log2m <= 11) {
+        uint16_t *hd;
+        rc = ensure_hll_doc16(sg, cs, P.dq.aggs[a].log2m, h, st, &hll_made, &hd);
+        if (rc) return rc;
+        ds.cols[P.dq.aggs[a].col_a].hll_doc16 = hd;
+        hll_doc16_used[(size_t)s * ncols + P.dq.aggs[a].col_a] = true;
+      } else {
+        uint32_t *hd;
+        rc = ensure_hll_doc(sg, cs, P.dq.aggs[a].log2m, h, st, &hll_made, &hd);
+        if (rc) return rc;
+        ds.cols[P.dq.aggs[a].col_a].hll_doc = hd;
       }
+      hll_doc_used[(size_t)s * ncols + P.dq.aggs[a].col_a] = true;
     }
-    for (int c = 0; c < ncols; c++)
-      if (col_remap[c]) ds.cols[c].remap = col_remap[c]->dev[s];
-    if (sg.num_docs == 0) continue;
-   // one entry per filter program (adjacent, so the programs of a segment read its columns back to back)
-   for (int prog = 0; prog < nprog; prog++) {
-    DevSeg ds = seg_ds;
-    ds.program = prog;
-    ds.seg_index = prog * nseg + s;
-    // filter program: validate the preorder ABI tree, then emit postfix with binary AND/OR
-    const int nb = q->filter_offsets ? q->filter_offsets[prog * nseg + s] : 0;
-    const int ne = q->filter_offsets ? q->filter_offsets[prog * nseg + s + 1] : 0;
-    const size_t node_begin = nodes.size();
-    ds.node_begin = (int32_t)node_begin;
-    int64_t hull_lo = 0, hull_hi = (int64_t)sg.num_docs - 1;  // candidate docs (inclusive)
-    if (ne > nb) {
-      std::vector<int> next(ne - nb);
-      std::string err;
-      int after = validate_tree(q->filter_nodes, nb, ne, nb, 0, ncols, next, err);
-      if (after < 0) return fail(PHIP_ERR_INVALID, "segment %d filter: %s", s, err.c_str());
-      if (after != ne) return fail(PHIP_ERR_INVALID, "segment %d filter: trailing nodes", s);
-      int32_t rc = PHIP_OK;
-      // A range / set leaf over a multi-value column: evaluated by mv_scan_kernel before the filter launch into dense
-      // doc words in the entry's interleaved inverted region; the device node is an inverted leaf over those words.
-      auto mv_leaf = [&](DevNode &dn, size_t ni, const phip_filter_node &fn, int32_t lo, int32_t hi,
-                         const std::vector<uint32_t> *set) {
-        if (!g_mv) {
-          rc = fail(PHIP_ERR_UNSUPPORTED, "a scan leaf over the multi-value column %s: this library was built without "
-                    "the multi-value kernels", sg.cols[colidx[s][fn.column]].name.c_str());
-          return;
-        }
-        int slot = 0;
-        for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
-        InvLeaf L{ni, s, colidx[s][fn.column], nullptr, num_entries, slot};  // (src: the inverted leaves' ids only)
-        L.mv = true;
-        L.mv_lo = lo;
-        L.mv_hi = hi;
-        L.mv_invert = fn.exclusive ? 1 : 0;
-        if (set) {
-          L.mv_set_words = (int32_t)set->size();
-          L.mv_set_off = blob.add(set->data(), set->size() * 4);
-        }
-        L.mv_stats = q->stats_programs == 0 || ((q->stats_programs >> prog) & 1u);
-        inv_leaves.push_back(L);
-        dn.leaf_kind = PHIP_LEAF_INVERTED;
-        dn.count = 0;
-        dn.bits = 0;
-      };
-      // An always-scan leaf over a single-value column whose ids are none or all of the dictionary's: a set leaf that
-      // matches no / every id (a range [0, card) would shift its span out of the id width when card == 2^bits, which
-      // is why such a range is otherwise folded to MATCH_ALL)
-      auto scan_const = [&](DevNode &dn, size_t ni, const ColumnStore &c, bool all) {
-        dn.leaf_kind = PHIP_LEAF_DICT_SET;
-        dn.lo = dn.hi = 0;
+  }
+  for (int k = 0; k < q->num_group_by; k++) {
+    DevCol &gc = ds.cols[q->group_by_columns[k]];
+    gc.remap = P.gb_dicts[k]->dev[s];
+    if (P.gb_dicts[k]->raw) gc.gb_base = P.gb_dicts[k]->raw_base;
+    if (!P.gb_dicts[k]->ids.empty()) gc.gb_ids = P.gb_dicts[k]->ids[s];  // a raw FLOAT / DOUBLE key: its id column
+    if (P.gb_radix[k] > P.gb_dicts[k]->card) {  // a null-key column: its null docs (if this segment has any)
+      gc.gb_nulls = segp[s]->cols[colidx[s][q->group_by_columns[k]]].nulls;
+      gc.gb_null_id = P.gb_dicts[k]->card;
+    }
+  }
+  for (int c = 0; c < ncols; c++)
+    if (col_remap[c]) ds.cols[c].remap = col_remap[c]->dev[s];
+  return PHIP_OK;
+}
+
+// A range / set leaf over a multi-value column: evaluated by mv_scan_kernel before the filter launch into dense
+// doc words in the entry's interleaved inverted region; the device node is an inverted leaf over those words.
+int32_t PlanBuilder::mv_leaf(int s, int prog, DevNode &dn, size_t ni, const phip_filter_node &fn, int32_t lo, int32_t hi,
+                             const std::vector<uint32_t> *set) {
+  if (!g_mv)
+    return fail(PHIP_ERR_UNSUPPORTED, "a scan leaf over the multi-value column %s: this library was built without "
+                "the multi-value kernels", segp[s]->cols[colidx[s][fn.column]].name.c_str());
+  InvLeaf L{ni, s, colidx[s][fn.column], nullptr, num_entries, entry_slot()};  // (src: the inverted leaves' ids only)
+  L.mv = true;
+  L.mv_lo = lo;
+  L.mv_hi = hi;
+  L.mv_invert = fn.exclusive ? 1 : 0;
+  if (set) {
+    L.mv_set_words = (int32_t)set->size();
+    L.mv_set_off = blob.add(set->data(), set->size() * 4);
+  }
+  L.mv_stats = q->stats_programs == 0 || ((q->stats_programs >> prog) & 1u);
+  inv_leaves.push_back(L);
+  dn.leaf_kind = PHIP_LEAF_INVERTED;
+  dn.count = 0;
+  dn.bits = 0;
+  return PHIP_OK;
+}
+
+// An always-scan leaf over a single-value column whose ids are none or all of the dictionary's: a set leaf that
+// matches no / every id (a range [0, card) would shift its span out of the id width when card == 2^bits, which
+// is why such a range is otherwise folded to MATCH_ALL)
+void PlanBuilder::scan_const(DevNode &dn, size_t ni, const ColumnStore &c, bool all) {
+  dn.leaf_kind = PHIP_LEAF_DICT_SET;
+  dn.lo = dn.hi = 0;
+  dn.exclusive = 0;
+  dn.bs_nruns = 0;
+  if (c.card <= 64) {
+    dn.small_set = 1;
+    dn.set_mask = all ? ~0ull : 0ull;
+  } else {
+    std::vector<uint32_t> b(ceil_div(c.card, 32) + 1, all ? ~0u : 0u);
+    dn.count = (int32_t)b.size();
+    aux_fix.push_back({ni, blob.add(b.data(), b.size() * 4)});
+  }
+}
+
+// leaf -> device node (the node's index is nodes.size(): the caller appends it)
+int32_t PlanBuilder::make_leaf(int s, int prog, const phip_filter_node &src, DevNode &dn) {
+  Segment &sg = *segp[s];
+  int32_t rc = PHIP_OK;
+  // PHIP_LEAF_FLAG_ALWAYS_SCAN (a dictionary REGEXP_LIKE leaf): the leaf stays a scan of the forward index even
+  // when its ids are none or all of the dictionary's, so the segment is not pruned and the scan is counted
+  phip_filter_node flagless = src;
+  flagless.exclusive = src.exclusive & 1;
+  const phip_filter_node &fn = flagless;
+  const bool always_scan = (src.exclusive & PHIP_LEAF_FLAG_ALWAYS_SCAN) != 0 &&
+                           (src.leaf_kind == PHIP_LEAF_DICT_RANGE || src.leaf_kind == PHIP_LEAF_DICT_SET);
+  memset(&dn, 0, sizeof(dn));
+  dn.op = DOP_LEAF;
+  dn.leaf_kind = fn.leaf_kind;
+  dn.column = fn.column;
+  dn.lo = fn.lo;
+  dn.hi = fn.hi;
+  dn.exclusive = fn.exclusive;
+  dn.count = fn.count;
+  dn.lds_off = -1;
+  dn.skip_to = -1;
+  const size_t ni = nodes.size();
+  ColumnStore *cs = (fn.leaf_kind >= PHIP_LEAF_DICT_RANGE && fn.leaf_kind != PHIP_LEAF_DOC_RANGES)
+                        ? &sg.cols[colidx[s][fn.column]]
+                        : nullptr;
+  if (cs) dn.bits = cs->bits;
+  switch (fn.leaf_kind) {
+    case PHIP_LEAF_DICT_RANGE:
+      if (no_dict(*cs)) { rc = fail(PHIP_ERR_INVALID, "dict leaf on raw column"); break; }
+      dn.lo = std::max(0, fn.lo);
+      dn.hi = std::min(cs->card, fn.hi);
+      if (always_scan && dn.hi <= dn.lo) {  // (no id to scan for: the empty id set says it)
+        rc = fail(PHIP_ERR_INVALID, "an always-scan DICT_RANGE leaf must hold an id: send an empty DICT_SET");
+        break;
+      }
+      if (is_mv(*cs)) {  // ANY value in the range (every doc has a value: the whole dictionary matches all)
+        if (dn.hi <= dn.lo && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+        else if (dn.lo == 0 && dn.hi == cs->card && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+        else rc = mv_leaf(s, prog, dn, ni, fn, dn.lo, dn.hi, nullptr);
         dn.exclusive = 0;
-        dn.bs_nruns = 0;
-        if (c.card <= 64) {
-          dn.small_set = 1;
-          dn.set_mask = all ? ~0ull : 0ull;
-        } else {
-          std::vector<uint32_t> b(ceil_div(c.card, 32) + 1, all ? ~0u : 0u);
-          dn.count = (int32_t)b.size();
-          aux_fix.push_back({ni, blob.add(b.data(), b.size() * 4)});
+        break;
+      }
+      if (always_scan) {
+        if (dn.lo == 0 && dn.hi == cs->card) scan_const(dn, ni, *cs, !fn.exclusive);
+        break;
+      }
+      if (dn.hi <= dn.lo) dn.leaf_kind = PHIP_LEAF_MATCH_NONE;
+      else if (dn.lo == 0 && dn.hi == cs->card) dn.leaf_kind = PHIP_LEAF_MATCH_ALL;
+      break;
+    case PHIP_LEAF_DICT_SET: {
+      if (no_dict(*cs)) { rc = fail(PHIP_ERR_INVALID, "dict leaf on raw column"); break; }
+      std::vector<uint32_t> bits(ceil_div(cs->card, 32) + 1, 0);
+      int32_t n_in = 0, mn = INT32_MAX, mx = -1;
+      for (int k = 0; k < fn.count; k++) {
+        int32_t id = fn.ids[k];
+        if (id < 0 || id >= cs->card) { rc = fail(PHIP_ERR_INVALID, "dict id %d out of range", id); break; }
+        if (!((bits[id >> 5] >> (id & 31)) & 1u)) n_in++;
+        bits[id >> 5] |= 1u << (id & 31);
+        mn = std::min(mn, id);
+        mx = std::max(mx, id);
+      }
+      if (rc) break;
+      // a contiguous id set (or its complement within the dictionary) is a dict-id range
+      const bool contiguous = n_in > 0 && mx - mn + 1 == n_in;
+      if (is_mv(*cs)) {
+        // inclusive: ANY value in the set; exclusive: NO value in it -- the complement of the inclusive doc set,
+        // never "any value outside the set" (so an exclusive set is not rewritten into its complement's range)
+        if (n_in == 0 && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+        else if (n_in == cs->card && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+        else if (contiguous) rc = mv_leaf(s, prog, dn, ni, fn, mn, mx + 1, nullptr);
+        else rc = mv_leaf(s, prog, dn, ni, fn, 0, 0, &bits);
+        dn.exclusive = 0;
+        break;
+      }
+      if (cs->bits <= kBitSliceMaxBits) {  // the matching ids as runs (the bit-sliced conjunction ORs <= 4)
+        int nr = 0;
+        bool prev = false;
+        for (int id = 0; id <= cs->card && nr <= 4; id++) {
+          const bool in = id < cs->card && (((bits[id >> 5] >> (id & 31)) & 1u) != 0) != (fn.exclusive != 0);
+          if (in && !prev) {
+            if (nr < 4) dn.bs_runs[nr] = (uint32_t)id;
+            nr++;
+          } else if (!in && prev && nr <= 4) {
+            dn.bs_runs[nr - 1] |= (uint32_t)(id - 1) << 16;
+          }
+          prev = in;
         }
-      };
-      // leaf -> device node
-      auto make_leaf = [&](const phip_filter_node &src) -> DevNode {
-        // PHIP_LEAF_FLAG_ALWAYS_SCAN (a dictionary REGEXP_LIKE leaf): the leaf stays a scan of the forward index even
-        // when its ids are none or all of the dictionary's, so the segment is not pruned and the scan is counted
-        phip_filter_node flagless = src;
-        flagless.exclusive = src.exclusive & 1;
-        const phip_filter_node &fn = flagless;
-        const bool always_scan = (src.exclusive & PHIP_LEAF_FLAG_ALWAYS_SCAN) != 0 &&
-                                 (src.leaf_kind == PHIP_LEAF_DICT_RANGE || src.leaf_kind == PHIP_LEAF_DICT_SET);
+        dn.bs_nruns = nr <= 4 && cs->card <= 65536 ? nr : 0;
+      }
+      if (always_scan && (n_in == 0 || n_in == cs->card)) {
+        scan_const(dn, ni, *cs, (n_in != 0) != (fn.exclusive != 0));
+      } else if (n_in == 0) {
+        dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+      } else if (n_in == cs->card) {
+        dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
+      } else if (contiguous && !fn.exclusive) {
+        dn.leaf_kind = PHIP_LEAF_DICT_RANGE;
+        dn.lo = mn;
+        dn.hi = mx + 1;
+      } else if (contiguous && fn.exclusive && (mn == 0 || mx == cs->card - 1)) {
+        dn.leaf_kind = PHIP_LEAF_DICT_RANGE;
+        dn.lo = mn == 0 ? mx + 1 : 0;
+        dn.hi = mn == 0 ? cs->card : mn;
+        dn.exclusive = 0;
+      } else if (cs->card <= 64) {
+        dn.small_set = 1;
+        dn.set_mask = (uint64_t)bits[0] | ((uint64_t)bits[1] << 32);
+        if (fn.exclusive) dn.set_mask = ~dn.set_mask;  // ids >= card never occur
+        dn.exclusive = 0;
+      } else {
+        dn.count = (int32_t)bits.size();  // bitset words (filter.hip: <= 64 words ride in one VGPR per lane)
+        aux_fix.push_back({ni, blob.add(bits.data(), bits.size() * 4)});
+      }
+      break;
+    }
+    case PHIP_LEAF_DOC_RANGES: {
+      int32_t prev = -1;
+      for (int k = 0; k < fn.count; k++) {
+        int32_t a0 = fn.ids[2 * k], a1 = fn.ids[2 * k + 1];
+        if (a0 <= prev || a1 < a0 || a1 >= sg.num_docs) {
+          rc = fail(PHIP_ERR_INVALID, "doc ranges must be sorted, disjoint and within numDocs");
+          break;
+        }
+        prev = a1;
+      }
+      if (rc) break;
+      if (fn.count == 0) {
+        dn.leaf_kind = PHIP_LEAF_MATCH_NONE;
+      } else {
+        dn.lo = fn.ids[0];
+        dn.hi = fn.ids[2 * fn.count - 1];
+        aux_fix.push_back({ni, blob.add(fn.ids, (size_t)fn.count * 8)});
+      }
+      break;
+    }
+    case PHIP_LEAF_RAW_RANGE:
+    case PHIP_LEAF_RAW_SET:
+      if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK) { rc = fail(PHIP_ERR_INVALID, "raw leaf on a column without raw values"); break; }
+      if (cs->type == PHIP_TYPE_STRING) { rc = fail(PHIP_ERR_INVALID, "STRING column: use the RAW_STRING leaves"); break; }
+      if (fn.leaf_kind == PHIP_LEAF_RAW_SET) {
+        // the kernel binary-searches the values (filter.hip sorted_contains): sorted, distinct, and for
+        // FLOAT / DOUBLE columns without NaN (IEEE equality never matches it)
+        const int64_t nv = fn.count / 2;
+        std::vector<int64_t> vi;
+        std::vector<double> vf;
+        const bool real = cs->type == PHIP_TYPE_FLOAT || cs->type == PHIP_TYPE_DOUBLE;
+        for (int64_t k = 0; k < nv; k++) {
+          int64_t x;
+          memcpy(&x, fn.ids + 2 * k, 8);
+          if (!real) {
+            vi.push_back(x);
+          } else {
+            double d;
+            memcpy(&d, &x, 8);
+            if (d == d) vf.push_back(d);
+          }
+        }
+        std::sort(vi.begin(), vi.end());
+        vi.erase(std::unique(vi.begin(), vi.end()), vi.end());
+        std::sort(vf.begin(), vf.end());
+        vf.erase(std::unique(vf.begin(), vf.end()), vf.end());  // (-0.0 and 0.0 compare equal: one kept)
+        dn.count = (int32_t)(real ? vf.size() : vi.size());
+        if (dn.count == 0) {
+          dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+          break;
+        }
+        aux_fix.push_back({ni, real ? blob.add(vf.data(), vf.size() * 8) : blob.add(vi.data(), vi.size() * 8)});
+        break;
+      }
+      aux_fix.push_back({ni, blob.add(fn.ids, (size_t)fn.count * 4)});
+      break;
+    case PHIP_LEAF_RAW_STRING_RANGE:
+    case PHIP_LEAF_RAW_STRING_SET:
+      if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK || cs->type != PHIP_TYPE_STRING || cs->str_off == nullptr) {
+        rc = fail(PHIP_ERR_INVALID, "raw STRING leaf on column %s, which holds no raw STRING values", cs->name.c_str());
+        break;
+      }
+      rc = raw_string_leaf(fn, dn, blob, aux_fix, ni);
+      break;
+    case PHIP_LEAF_RAW_STRING_MATCH: {
+      // REGEXP_LIKE / LIKE over a raw STRING column: evaluated by strmatch_kernel before the filter launch into
+      // dense doc words in the entry's interleaved inverted region; the device node is an inverted leaf over them
+      if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK || cs->type != PHIP_TYPE_STRING || cs->str_off == nullptr) {
+        rc = fail(PHIP_ERR_INVALID, "raw STRING match leaf on column %s, which holds no raw STRING values", cs->name.c_str());
+        break;
+      }
+      StrMatchImage img;
+      if ((rc = strmatch_image(fn.ids, fn.count, &img))) break;
+      if (!g_strmatch) {
+        rc = fail(PHIP_ERR_UNSUPPORTED, "a match leaf over column %s: this library was built without the string-match "
+                  "kernel", cs->name.c_str());
+        break;
+      }
+      InvLeaf L{ni, s, colidx[s][fn.column], nullptr, num_entries, entry_slot()};
+      L.sm = true;
+      L.mv_invert = fn.exclusive ? 1 : 0;
+      L.mv_stats = q->stats_programs == 0 || ((q->stats_programs >> prog) & 1u);
+      L.sm_table_words = (int32_t)img.words.size();
+      L.sm_table_off = blob.add(img.words.data(), img.words.size() * 4);
+      L.sm_states = img.num_states;
+      L.sm_classes = img.num_classes;
+      L.sm_start = img.start;
+      L.sm_absorb_end = img.absorb_end;
+      L.sm_accept_begin = img.accept_begin;
+      L.sm_accept_end = img.accept_end;
+      inv_leaves.push_back(L);
+      dn.leaf_kind = PHIP_LEAF_INVERTED;
+      dn.exclusive = 0;
+      dn.count = 0;
+      dn.bits = 0;
+      break;
+    }
+    case PHIP_LEAF_NULL:
+      // the column's resident null doc words, read like an inverted leaf's words (one 256-byte region per tile)
+      if (cs->nulls == nullptr) {
+        dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
+        dn.exclusive = 0;
+        break;
+      }
+      dn.leaf_kind = PHIP_LEAF_INVERTED;
+      dn.aux = cs->nulls;
+      dn.aux_stride = 32;
+      dn.count = 0;
+      dn.bits = 0;
+      break;
+    case PHIP_LEAF_INVERTED:
+      if (cs->inv_begin.empty()) { rc = fail(PHIP_ERR_INVALID, "column %s has no inverted index", cs->name.c_str()); break; }
+      inv_leaves.push_back({ni, s, colidx[s][fn.column], &src, num_entries, entry_slot()});
+      break;
+    default: break;
+  }
+  return rc;
+}
+
+// One (segment, program) entry: the filter program's preorder ABI tree validated and emitted as postfix with binary
+// AND / OR, its stack depth and candidate-doc hull; an entry with a candidate doc joins the work list.
+int32_t PlanBuilder::lower_filter_program(int s, int prog, const DevSeg &seg_ds) {
+  const Segment &sg = *segp[s];
+  DevSeg ds = seg_ds;
+  ds.program = prog;
+  ds.seg_index = prog * P.nseg + s;
+  // filter program: validate the preorder ABI tree, then emit postfix with binary AND/OR
+  const int nb = q->filter_offsets ? q->filter_offsets[prog * P.nseg + s] : 0;
+  const int ne = q->filter_offsets ? q->filter_offsets[prog * P.nseg + s + 1] : 0;
+  const size_t node_begin = nodes.size();
+  ds.node_begin = (int32_t)node_begin;
+  int64_t hull_lo = 0, hull_hi = (int64_t)sg.num_docs - 1;  // candidate docs (inclusive)
+  if (ne > nb) {
+    std::vector<int> next(ne - nb);
+    std::string err;
+    int after = validate_tree(q->filter_nodes, nb, ne, nb, 0, ncols, next, err);
+    if (after < 0) return fail(PHIP_ERR_INVALID, "segment %d filter: %s", s, err.c_str());
+    if (after != ne) return fail(PHIP_ERR_INVALID, "segment %d filter: trailing nodes", s);
+    int32_t rc = PHIP_OK;
+    // recursive postfix emission (depth bounded by validate_tree)
+    std::function<void(int)> emit = [&](int idx) {
+      if (rc) return;
+      const phip_filter_node &fn = q->filter_nodes[idx];
+      if (fn.op == PHIP_NODE_LEAF) {
+        DevNode dn;
+        rc = make_leaf(s, prog, fn, dn);
+        nodes.push_back(dn);
+        return;
+      }
+      if (fn.op == PHIP_NODE_NOT) {
+        emit(idx + 1);
         DevNode dn;
         memset(&dn, 0, sizeof(dn));
-        dn.op = DOP_LEAF;
-        dn.leaf_kind = fn.leaf_kind;
-        dn.column = fn.column;
-        dn.lo = fn.lo;
-        dn.hi = fn.hi;
-        dn.exclusive = fn.exclusive;
-        dn.count = fn.count;
+        dn.op = DOP_NOT;
         dn.lds_off = -1;
         dn.skip_to = -1;
-        const size_t ni = nodes.size();
-        ColumnStore *cs = (fn.leaf_kind >= PHIP_LEAF_DICT_RANGE && fn.leaf_kind != PHIP_LEAF_DOC_RANGES)
-                              ? &sg.cols[colidx[s][fn.column]]
-                              : nullptr;
-        if (cs) dn.bits = cs->bits;
-        switch (fn.leaf_kind) {
-          case PHIP_LEAF_DICT_RANGE:
-            if (no_dict(*cs)) { rc = fail(PHIP_ERR_INVALID, "dict leaf on raw column"); break; }
-            dn.lo = std::max(0, fn.lo);
-            dn.hi = std::min(cs->card, fn.hi);
-            if (always_scan && dn.hi <= dn.lo) {  // (no id to scan for: the empty id set says it)
-              rc = fail(PHIP_ERR_INVALID, "an always-scan DICT_RANGE leaf must hold an id: send an empty DICT_SET");
-              break;
-            }
-            if (is_mv(*cs)) {  // ANY value in the range (every doc has a value: the whole dictionary matches all)
-              if (dn.hi <= dn.lo && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-              else if (dn.lo == 0 && dn.hi == cs->card && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
-              else mv_leaf(dn, ni, fn, dn.lo, dn.hi, nullptr);
-              dn.exclusive = 0;
-              break;
-            }
-            if (always_scan) {
-              if (dn.lo == 0 && dn.hi == cs->card) scan_const(dn, ni, *cs, !fn.exclusive);
-              break;
-            }
-            if (dn.hi <= dn.lo) dn.leaf_kind = PHIP_LEAF_MATCH_NONE;
-            else if (dn.lo == 0 && dn.hi == cs->card) dn.leaf_kind = PHIP_LEAF_MATCH_ALL;
-            break;
-          case PHIP_LEAF_DICT_SET: {
-            if (no_dict(*cs)) { rc = fail(PHIP_ERR_INVALID, "dict leaf on raw column"); break; }
-            std::vector<uint32_t> bits(ceil_div(cs->card, 32) + 1, 0);
-            int32_t n_in = 0, mn = INT32_MAX, mx = -1;
-            for (int k = 0; k < fn.count; k++) {
-              int32_t id = fn.ids[k];
-              if (id < 0 || id >= cs->card) { rc = fail(PHIP_ERR_INVALID, "dict id %d out of range", id); break; }
-              if (!((bits[id >> 5] >> (id & 31)) & 1u)) n_in++;
-              bits[id >> 5] |= 1u << (id & 31);
-              mn = std::min(mn, id);
-              mx = std::max(mx, id);
-            }
-            if (rc) break;
-            // a contiguous id set (or its complement within the dictionary) is a dict-id range
-            const bool contiguous = n_in > 0 && mx - mn + 1 == n_in;
-            if (is_mv(*cs)) {
-              // inclusive: ANY value in the set; exclusive: NO value in it -- the complement of the inclusive doc set,
-              // never "any value outside the set" (so an exclusive set is not rewritten into its complement's range)
-              if (n_in == 0 && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-              else if (n_in == cs->card && !always_scan) dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
-              else if (contiguous) mv_leaf(dn, ni, fn, mn, mx + 1, nullptr);
-              else mv_leaf(dn, ni, fn, 0, 0, &bits);
-              dn.exclusive = 0;
-              break;
-            }
-            if (cs->bits <= kBitSliceMaxBits) {  // the matching ids as runs (the bit-sliced conjunction ORs <= 4)
-              int nr = 0;
-              bool prev = false;
-              for (int id = 0; id <= cs->card && nr <= 4; id++) {
-                const bool in = id < cs->card && (((bits[id >> 5] >> (id & 31)) & 1u) != 0) != (fn.exclusive != 0);
-                if (in && !prev) {
-                  if (nr < 4) dn.bs_runs[nr] = (uint32_t)id;
-                  nr++;
-                } else if (!in && prev && nr <= 4) {
-                  dn.bs_runs[nr - 1] |= (uint32_t)(id - 1) << 16;
-                }
-                prev = in;
-              }
-              dn.bs_nruns = nr <= 4 && cs->card <= 65536 ? nr : 0;
-            }
-            if (always_scan && (n_in == 0 || n_in == cs->card)) {
-              scan_const(dn, ni, *cs, (n_in != 0) != (fn.exclusive != 0));
-            } else if (n_in == 0) {
-              dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-            } else if (n_in == cs->card) {
-              dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_NONE : PHIP_LEAF_MATCH_ALL;
-            } else if (contiguous && !fn.exclusive) {
-              dn.leaf_kind = PHIP_LEAF_DICT_RANGE;
-              dn.lo = mn;
-              dn.hi = mx + 1;
-            } else if (contiguous && fn.exclusive && (mn == 0 || mx == cs->card - 1)) {
-              dn.leaf_kind = PHIP_LEAF_DICT_RANGE;
-              dn.lo = mn == 0 ? mx + 1 : 0;
-              dn.hi = mn == 0 ? cs->card : mn;
-              dn.exclusive = 0;
-            } else if (cs->card <= 64) {
-              dn.small_set = 1;
-              dn.set_mask = (uint64_t)bits[0] | ((uint64_t)bits[1] << 32);
-              if (fn.exclusive) dn.set_mask = ~dn.set_mask;  // ids >= card never occur
-              dn.exclusive = 0;
-            } else {
-              dn.count = (int32_t)bits.size();  // bitset words (filter.hip: <= 64 words ride in one VGPR per lane)
-              aux_fix.push_back({ni, blob.add(bits.data(), bits.size() * 4)});
-            }
-            break;
-          }
-          case PHIP_LEAF_DOC_RANGES: {
-            int32_t prev = -1;
-            for (int k = 0; k < fn.count; k++) {
-              int32_t a0 = fn.ids[2 * k], a1 = fn.ids[2 * k + 1];
-              if (a0 <= prev || a1 < a0 || a1 >= sg.num_docs) {
-                rc = fail(PHIP_ERR_INVALID, "doc ranges must be sorted, disjoint and within numDocs");
-                break;
-              }
-              prev = a1;
-            }
-            if (rc) break;
-            if (fn.count == 0) {
-              dn.leaf_kind = PHIP_LEAF_MATCH_NONE;
-            } else {
-              dn.lo = fn.ids[0];
-              dn.hi = fn.ids[2 * fn.count - 1];
-              aux_fix.push_back({ni, blob.add(fn.ids, (size_t)fn.count * 8)});
-            }
-            break;
-          }
-          case PHIP_LEAF_RAW_RANGE:
-          case PHIP_LEAF_RAW_SET:
-            if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK) { rc = fail(PHIP_ERR_INVALID, "raw leaf on a column without raw values"); break; }
-            if (cs->type == PHIP_TYPE_STRING) { rc = fail(PHIP_ERR_INVALID, "STRING column: use the RAW_STRING leaves"); break; }
-            if (fn.leaf_kind == PHIP_LEAF_RAW_SET) {
-              // the kernel binary-searches the values (filter.hip sorted_contains): sorted, distinct, and for
-              // FLOAT / DOUBLE columns without NaN (IEEE equality never matches it)
-              const int64_t nv = fn.count / 2;
-              std::vector<int64_t> vi;
-              std::vector<double> vf;
-              const bool real = cs->type == PHIP_TYPE_FLOAT || cs->type == PHIP_TYPE_DOUBLE;
-              for (int64_t k = 0; k < nv; k++) {
-                int64_t x;
-                memcpy(&x, fn.ids + 2 * k, 8);
-                if (!real) {
-                  vi.push_back(x);
-                } else {
-                  double d;
-                  memcpy(&d, &x, 8);
-                  if (d == d) vf.push_back(d);
-                }
-              }
-              std::sort(vi.begin(), vi.end());
-              vi.erase(std::unique(vi.begin(), vi.end()), vi.end());
-              std::sort(vf.begin(), vf.end());
-              vf.erase(std::unique(vf.begin(), vf.end()), vf.end());  // (-0.0 and 0.0 compare equal: one kept)
-              dn.count = (int32_t)(real ? vf.size() : vi.size());
-              if (dn.count == 0) {
-                dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-                break;
-              }
-              aux_fix.push_back({ni, real ? blob.add(vf.data(), vf.size() * 8) : blob.add(vi.data(), vi.size() * 8)});
-              break;
-            }
-            aux_fix.push_back({ni, blob.add(fn.ids, (size_t)fn.count * 4)});
-            break;
-          case PHIP_LEAF_RAW_STRING_RANGE:
-          case PHIP_LEAF_RAW_STRING_SET:
-            if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK || cs->type != PHIP_TYPE_STRING || cs->str_off == nullptr) {
-              rc = fail(PHIP_ERR_INVALID, "raw STRING leaf on column %s, which holds no raw STRING values", cs->name.c_str());
-              break;
-            }
-            rc = raw_string_leaf(fn, dn, blob, aux_fix, ni);
-            break;
-          case PHIP_LEAF_RAW_STRING_MATCH: {
-            // REGEXP_LIKE / LIKE over a raw STRING column: evaluated by strmatch_kernel before the filter launch into
-            // dense doc words in the entry's interleaved inverted region; the device node is an inverted leaf over them
-            if (cs->fwd_kind != PHIP_FWD_RAW_CHUNK || cs->type != PHIP_TYPE_STRING || cs->str_off == nullptr) {
-              rc = fail(PHIP_ERR_INVALID, "raw STRING match leaf on column %s, which holds no raw STRING values", cs->name.c_str());
-              break;
-            }
-            StrMatchImage img;
-            if ((rc = strmatch_image(fn.ids, fn.count, &img))) break;
-            if (!g_strmatch) {
-              rc = fail(PHIP_ERR_UNSUPPORTED, "a match leaf over column %s: this library was built without the string-match "
-                        "kernel", cs->name.c_str());
-              break;
-            }
-            int slot = 0;
-            for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
-            InvLeaf L{ni, s, colidx[s][fn.column], nullptr, num_entries, slot};
-            L.sm = true;
-            L.mv_invert = fn.exclusive ? 1 : 0;
-            L.mv_stats = q->stats_programs == 0 || ((q->stats_programs >> prog) & 1u);
-            L.sm_table_words = (int32_t)img.words.size();
-            L.sm_table_off = blob.add(img.words.data(), img.words.size() * 4);
-            L.sm_states = img.num_states;
-            L.sm_classes = img.num_classes;
-            L.sm_start = img.start;
-            L.sm_absorb_end = img.absorb_end;
-            L.sm_accept_begin = img.accept_begin;
-            L.sm_accept_end = img.accept_end;
-            inv_leaves.push_back(L);
-            dn.leaf_kind = PHIP_LEAF_INVERTED;
-            dn.exclusive = 0;
-            dn.count = 0;
-            dn.bits = 0;
-            break;
-          }
-          case PHIP_LEAF_NULL:
-            // the column's resident null doc words, read like an inverted leaf's words (one 256-byte region per tile)
-            if (cs->nulls == nullptr) {
-              dn.leaf_kind = fn.exclusive ? PHIP_LEAF_MATCH_ALL : PHIP_LEAF_MATCH_NONE;
-              dn.exclusive = 0;
-              break;
-            }
-            dn.leaf_kind = PHIP_LEAF_INVERTED;
-            dn.aux = cs->nulls;
-            dn.aux_stride = 32;
-            dn.count = 0;
-            dn.bits = 0;
-            break;
-          case PHIP_LEAF_INVERTED:
-            if (cs->inv_begin.empty()) { rc = fail(PHIP_ERR_INVALID, "column %s has no inverted index", cs->name.c_str()); break; }
-            {
-              int slot = 0;
-              for (const InvLeaf &o : inv_leaves) slot += o.entry == num_entries ? 1 : 0;
-              inv_leaves.push_back({ni, s, colidx[s][fn.column], &src, num_entries, slot});
-            }
-            break;
-          default: break;
-        }
-        return dn;
-      };
-      // recursive postfix emission (depth bounded by validate_tree)
-      std::function<void(int)> emit = [&](int idx) {
-        if (rc) return;
-        const phip_filter_node &fn = q->filter_nodes[idx];
-        if (fn.op == PHIP_NODE_LEAF) {
-          DevNode dn = make_leaf(fn);
-          nodes.push_back(dn);
-          return;
-        }
-        if (fn.op == PHIP_NODE_NOT) {
-          emit(idx + 1);
+        nodes.push_back(dn);
+        return;
+      }
+      int c = idx + 1;
+      for (int k = 0; k < fn.num_children && !rc; k++) {
+        const size_t first = nodes.size();
+        emit(c);
+        if (k > 0) {
           DevNode dn;
           memset(&dn, 0, sizeof(dn));
-          dn.op = DOP_NOT;
+          dn.op = fn.op == PHIP_NODE_AND ? DOP_AND : DOP_OR;
           dn.lds_off = -1;
           dn.skip_to = -1;
           nodes.push_back(dn);
-          return;
+          // the child's first node is its leftmost leaf: skip the child when the node is decided
+          nodes[first].skip_kind = fn.op == PHIP_NODE_AND ? SKIP_IF_NONE : SKIP_IF_ALL;
+          nodes[first].skip_to = (int32_t)nodes.size();
         }
-        int c = idx + 1;
-        for (int k = 0; k < fn.num_children && !rc; k++) {
-          const size_t first = nodes.size();
-          emit(c);
-          if (k > 0) {
-            DevNode dn;
-            memset(&dn, 0, sizeof(dn));
-            dn.op = fn.op == PHIP_NODE_AND ? DOP_AND : DOP_OR;
-            dn.lds_off = -1;
-            dn.skip_to = -1;
-            nodes.push_back(dn);
-            // the child's first node is its leftmost leaf: skip the child when the node is decided
-            nodes[first].skip_kind = fn.op == PHIP_NODE_AND ? SKIP_IF_NONE : SKIP_IF_ALL;
-            nodes[first].skip_to = (int32_t)nodes.size();
-          }
-          c = next[c - nb];
-        }
-      };
-      emit(nb);
-      if (rc) return rc;
-      // stack depth and candidate-doc hull (SortedIndexBasedFilterOperator ranges under ANDs)
-      struct Hull {
-        int64_t lo, hi;
-      };
-      std::vector<Hull> hst;
-      int sp = 0, maxsp = 0;
-      const int64_t full_hi = (int64_t)sg.num_docs - 1;
-      for (size_t i = node_begin; i < nodes.size(); i++) {
-        const DevNode &dn = nodes[i];
-        if (dn.op == DOP_LEAF) {
-          sp++;
-          Hull h{0, full_hi};
-          if (dn.leaf_kind == PHIP_LEAF_MATCH_NONE) h = {1, 0};
-          if (dn.leaf_kind == PHIP_LEAF_DOC_RANGES) h = {dn.lo, dn.hi};  // first start .. last end
-          hst.push_back(h);
-        } else if (dn.op == DOP_NOT) {
-          hst.back() = {0, full_hi};
-        } else {
-          sp--;
-          Hull b = hst.back();
-          hst.pop_back();
-          Hull a = hst.back();
-          if (dn.op == DOP_AND) hst.back() = {std::max(a.lo, b.lo), std::min(a.hi, b.hi)};
-          else if (a.lo > a.hi) hst.back() = b;
-          else if (b.lo > b.hi) hst.back() = a;
-          else hst.back() = {std::min(a.lo, b.lo), std::max(a.hi, b.hi)};
-        }
-        maxsp = std::max(maxsp, sp);
+        c = next[c - nb];
       }
-      if (maxsp > kMaxFilterStack) return fail(PHIP_ERR_UNSUPPORTED, "segment %d filter needs stack depth %d", s, maxsp);
-      hull_lo = hst.back().lo;
-      hull_hi = hst.back().hi;
+    };
+    emit(nb);
+    if (rc) return rc;
+    // stack depth and candidate-doc hull (SortedIndexBasedFilterOperator ranges under ANDs)
+    struct Hull {
+      int64_t lo, hi;
+    };
+    std::vector<Hull> hst;
+    int sp = 0, maxsp = 0;
+    const int64_t full_hi = (int64_t)sg.num_docs - 1;
+    for (size_t i = node_begin; i < nodes.size(); i++) {
+      const DevNode &dn = nodes[i];
+      if (dn.op == DOP_LEAF) {
+        sp++;
+        Hull h{0, full_hi};
+        if (dn.leaf_kind == PHIP_LEAF_MATCH_NONE) h = {1, 0};
+        if (dn.leaf_kind == PHIP_LEAF_DOC_RANGES) h = {dn.lo, dn.hi};  // first start .. last end
+        hst.push_back(h);
+      } else if (dn.op == DOP_NOT) {
+        hst.back() = {0, full_hi};
+      } else {
+        sp--;
+        Hull b = hst.back();
+        hst.pop_back();
+        Hull a = hst.back();
+        if (dn.op == DOP_AND) hst.back() = {std::max(a.lo, b.lo), std::min(a.hi, b.hi)};
+        else if (a.lo > a.hi) hst.back() = b;
+        else if (b.lo > b.hi) hst.back() = a;
+        else hst.back() = {std::min(a.lo, b.lo), std::max(a.hi, b.hi)};
+      }
+      maxsp = std::max(maxsp, sp);
     }
-    ds.node_end = (int32_t)nodes.size();
-    num_entries++;
-    entry_has_work.push_back(hull_lo <= hull_hi);
-    if (hull_lo > hull_hi) continue;  // no candidate doc: the segment is pruned (no work)
-    ds.tile0 = (int32_t)(hull_lo / kTileDocs);
-    ds.num_work = (int32_t)(hull_hi / kTileDocs - ds.tile0 + 1);
-    ds.work_begin = (int32_t)total_work;
-    total_work += ds.num_work;
-    dsegs.push_back(ds);
-   }
+    if (maxsp > kMaxFilterStack) return fail(PHIP_ERR_UNSUPPORTED, "segment %d filter needs stack depth %d", s, maxsp);
+    hull_lo = hst.back().lo;
+    hull_hi = hst.back().hi;
   }
-  if (hll_made) HIP_TRY(hipStreamSynchronize(st));
-  if (total_work > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many tiles in one query");
-  dq.total_work = (int32_t)total_work;
-  if (group_by && gb_key_space > ((int64_t)1 << 22) && tl_node_docs == 0) {  // (node parts: sized by the node's docs)
+  ds.node_end = (int32_t)nodes.size();
+  num_entries++;
+  entry_has_work.push_back(hull_lo <= hull_hi);
+  if (hull_lo > hull_hi) return PHIP_OK;  // no candidate doc: the segment is pruned (no work)
+  ds.tile0 = (int32_t)(hull_lo / kTileDocs);
+  ds.num_work = (int32_t)(hull_hi / kTileDocs - ds.tile0 + 1);
+  ds.work_begin = (int32_t)P.total_work;
+  P.total_work += ds.num_work;
+  P.dsegs.push_back(ds);
+  return PHIP_OK;
+}
+
+// The group table's size once the work list is known (plan_group_table sized it from the segments' docs).
+int32_t PlanBuilder::size_hash_table() {
+  if (P.group_by && gb_key_space > ((int64_t)1 << 22) && tl_node_docs == 0) {  // (node parts: sized by the node's docs)
     // Re-size a large group table from the docs of the work tiles (sorted-index pruning already cut them):
     // only those docs can create groups, and the table is cleared and compacted on every execution
     // (BenchmarkQueries STARTREE_FILTER_QUERY: one candidate tile, yet 2 x 10M hash slots before).
-    const int64_t work_docs = std::max<int64_t>(1, total_work * (int64_t)kTileDocs);
+    const int64_t work_docs = std::max<int64_t>(1, P.total_work * (int64_t)kTileDocs);
     if (gb_force_hash || gb_key_space > ((int64_t)1 << 26) || gb_key_space > 4 * work_docs) {
       const int64_t bound = std::max<int64_t>(1, std::min<int64_t>(gb_key_space, work_docs));
       int64_t cap = 1024;
       while (cap < 2 * bound) cap <<= 1;
       if (const char *hc = getenv("PHIP_GB_HASH_CAP"))
         cap = std::max<int64_t>(64, std::min<int64_t>(cap, (int64_t)1 << (63 - __builtin_clzll((uint64_t)std::max(2LL, atoll(hc))))));
-      if (dq.mode != GB_HASH || cap < dq.num_groups) {
-        const int64_t per_slot = 8 + 8 * (1 + (int64_t)naggs);
+      if (P.dq.mode != GB_HASH || cap < P.dq.num_groups) {
+        const int64_t per_slot = 8 + 8 * (1 + (int64_t)P.naggs);
         if (cap * per_slot > ((int64_t)24 << 30))
           return fail(PHIP_ERR_UNSUPPORTED, "group-by hash table of %lld slots exceeds the memory budget", (long long)cap);
-        dq.num_groups = cap;
-        dq.mode = GB_HASH;
+        P.dq.num_groups = cap;
+        P.dq.mode = GB_HASH;
       }
     }
   }
   // (the re-size above may have turned a large dense key space into a hash table after the first check)
-  if (!P.dist_agg.empty() && group_by && dq.mode == GB_HASH)
+  if (!P.dist_agg.empty() && P.group_by && P.dq.mode == GB_HASH)
     return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNT / value counts over a hash-table group-by key space");
-  dq.num_segs = (int32_t)dsegs.size();
-  const size_t segs_off = blob.reserve(sizeof(DevSeg) * std::max<size_t>(dsegs.size(), 1));
+  return PHIP_OK;
+}
 
-  // inverted leaves: dense doc words per leaf + roaring container tasks. The L inverted leaves of one
-  // (segment, program) entry are interleaved per 2048-doc tile -- tile t holds leaf 0's 32 words, then leaf
-  // 1's, ... -- so the filter kernel stages all of them with one L x 256-byte LDS-DMA region per tile instead of
-  // L quarter-filled 256-byte ones.
-  std::vector<RoaringTask> tasks;
-  size_t inv_words_total = 0;
+// Inverted leaves: dense doc words per leaf + roaring container tasks. The L inverted leaves of one
+// (segment, program) entry are interleaved per 2048-doc tile -- tile t holds leaf 0's 32 words, then leaf
+// 1's, ... -- so the filter kernel stages all of them with one L x 256-byte LDS-DMA region per tile instead of
+// L quarter-filled 256-byte ones. MV scan leaves and string-match leaves get their tasks here too.
+int32_t PlanBuilder::stage_inverted_leaves() {
   std::vector<size_t> inv_word_off(inv_leaves.size()), inv_word_nw(inv_leaves.size());
   std::vector<int> entry_leaves(num_entries, 0);
   std::vector<size_t> entry_off(num_entries, 0);
   for (const InvLeaf &L : inv_leaves) entry_leaves[L.entry]++;
   for (size_t i = 0; i < inv_leaves.size(); i++) {
     const InvLeaf &L = inv_leaves[i];
-    const Segment &sg = *segs[L.seg];
+    const Segment &sg = *segp[L.seg];
     size_t nw = (size_t)std::max(round_up(sg.num_docs, 65536), round_up(sg.num_docs, kTileDocs)) / 64;  // whole keys
     inv_word_nw[i] = nw;
     if (L.slot == 0) {
-      entry_off[L.entry] = inv_words_total;
-      inv_words_total += nw * entry_leaves[L.entry];
+      entry_off[L.entry] = P.inv_words_total;
+      P.inv_words_total += nw * entry_leaves[L.entry];
     }
     inv_word_off[i] = entry_off[L.entry] + 32 * (size_t)L.slot;
   }
-  std::vector<int32_t> node_inv_stride(nodes.size(), 0);   // u64 words per tile of an inverted leaf's aux
-  std::vector<int32_t> node_inv_slot(nodes.size(), 0);
-  std::vector<int32_t> node_inv_leaves(nodes.size(), 0);
-  void *inv_words = nullptr;
-  if (inv_words_total) {
-    int32_t rc = P.alloc(inv_words_total * 8, &inv_words);
+  node_inv_slot.assign(nodes.size(), 0);
+  node_inv_leaves.assign(nodes.size(), 0);
+  if (P.inv_words_total) {
+    int32_t rc = P.alloc(P.inv_words_total * 8, &P.inv_words);
     if (rc) return rc;
   }
   std::vector<RoaringGroup> rgroups;
-  std::vector<MvScanTask> mv_tasks;
-  std::vector<size_t> mv_set_offs;
-  int64_t mv_total_tiles = 0, mv_entries = 0;
-  std::vector<StrMatchTask> sm_tasks;
-  std::vector<size_t> sm_table_offs;
-  int64_t sm_total_tiles = 0, sm_entries = 0;
-  int32_t sm_table_words = 0;
+  int64_t mv_tiles = 0, sm_tiles = 0;  // (P.mv_total_tiles / P.sm_total_tiles: int32 once they are bounded)
   for (size_t i = 0; i < inv_leaves.size(); i++) {
     const InvLeaf &L = inv_leaves[i];
-    const ColumnStore &cs = segs[L.seg]->cols[L.col];
-    uint64_t *words = (uint64_t *)inv_words + inv_word_off[i];
+    const ColumnStore &cs = segp[L.seg]->cols[L.col];
+    uint64_t *words = (uint64_t *)P.inv_words + inv_word_off[i];
     const int32_t tile_words = 32 * entry_leaves[L.entry];
     nodes[L.node].aux = words;
     nodes[L.node].aux_stride = tile_words;
-    node_inv_stride[L.node] = tile_words;
     node_inv_slot[L.node] = L.slot;
     node_inv_leaves[L.node] = entry_leaves[L.entry];
     if (L.mv) {
@@ -4359,17 +4462,17 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       t.offsets = cs.mv_off;
       t.out = words;
       t.tile_words = tile_words;
-      t.num_docs = segs[L.seg]->num_docs;
+      t.num_docs = segp[L.seg]->num_docs;
       t.num_tiles = (int32_t)(inv_word_nw[i] / 32);
-      t.tile_begin = mv_total_tiles;
+      t.tile_begin = mv_tiles;
       t.bits = cs.bits;
       t.lo = L.mv_lo;
       t.hi = L.mv_hi;
       t.invert = L.mv_invert;
       t.set_words = L.mv_set_words;
-      mv_total_tiles += t.num_tiles;
-      if (mv_total_tiles > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many multi-value scan tiles in one query");
-      if (L.mv_stats) mv_entries += cs.total_values;
+      mv_tiles += t.num_tiles;
+      if (mv_tiles > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many multi-value scan tiles in one query");
+      if (L.mv_stats) P.mv_entries += cs.total_values;
       mv_tasks.push_back(t);
       mv_set_offs.push_back(L.mv_set_words > 0 ? L.mv_set_off : SIZE_MAX);
       continue;
@@ -4382,9 +4485,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       t.offsets = cs.str_off;
       t.out = words;
       t.tile_words = tile_words;
-      t.num = segs[L.seg]->num_docs;
+      t.num = segp[L.seg]->num_docs;
       t.num_tiles = (int32_t)(inv_word_nw[i] / 32);
-      t.tile_begin = (int32_t)sm_total_tiles;
+      t.tile_begin = (int32_t)sm_tiles;
       t.num_states = L.sm_states;
       t.num_classes = L.sm_classes;
       t.start = L.sm_start;
@@ -4392,15 +4495,15 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       t.accept_begin = L.sm_accept_begin;
       t.accept_end = L.sm_accept_end;
       t.invert = L.mv_invert;
-      sm_total_tiles += t.num_tiles;
-      if (sm_total_tiles > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many string-match tiles in one query");
-      if (L.mv_stats) sm_entries += segs[L.seg]->num_docs;
-      sm_table_words = std::max(sm_table_words, L.sm_table_words);
+      sm_tiles += t.num_tiles;
+      if (sm_tiles > INT32_MAX / 2) return fail(PHIP_ERR_UNSUPPORTED, "too many string-match tiles in one query");
+      if (L.mv_stats) P.sm_entries += segp[L.seg]->num_docs;
+      P.sm_table_words = std::max(P.sm_table_words, L.sm_table_words);
       sm_tasks.push_back(t);
       sm_table_offs.push_back(L.sm_table_off);
       continue;
     }
-    const size_t first = tasks.size();
+    const size_t first = P.tasks.size();
     for (int k = 0; k < L.src->count; k++) {
       int32_t id = L.src->ids[k];
       if (id < 0 || id >= cs.card) return fail(PHIP_ERR_INVALID, "inverted dict id %d out of range", id);
@@ -4413,19 +4516,19 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         t.kind = ct.kind;
         t.card = ct.card;
         t.pad = 0;
-        tasks.push_back(t);
+        P.tasks.push_back(t);
       }
     }
     // group the leaf's containers by key (one LDS-decoding workgroup per key); every key of the leaf's words
     // gets a group -- one without containers stores zeros -- so the words need no clearing pass
-    std::stable_sort(tasks.begin() + first, tasks.end(),
+    std::stable_sort(P.tasks.begin() + first, P.tasks.end(),
                      [](const RoaringTask &a, const RoaringTask &b) { return a.key < b.key; });
-    if (tasks.size() > (size_t)INT32_MAX) return fail(PHIP_ERR_UNSUPPORTED, "too many inverted-index containers");
+    if (P.tasks.size() > (size_t)INT32_MAX) return fail(PHIP_ERR_UNSUPPORTED, "too many inverted-index containers");
     const int32_t nkeys = (int32_t)(inv_word_nw[i] / 1024);
     size_t t = first;
     for (int32_t key = 0; key < nkeys; key++) {
       size_t e = t;
-      while (e < tasks.size() && tasks[e].key == key) e++;
+      while (e < P.tasks.size() && P.tasks[e].key == key) e++;
       RoaringGroup g;
       g.out_words = words;
       g.task_begin = (int32_t)t;
@@ -4435,29 +4538,36 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       rgroups.push_back(g);
       t = e;
     }
-    if (t != tasks.size()) return fail(PHIP_ERR_INVALID, "inverted-index container key beyond the segment's docs");
+    if (t != P.tasks.size()) return fail(PHIP_ERR_INVALID, "inverted-index container key beyond the segment's docs");
   }
-  const size_t tasks_off = tasks.empty() ? 0 : blob.add(tasks.data(), tasks.size() * sizeof(RoaringTask));
-  const size_t rgroups_off = rgroups.empty() ? 0 : blob.add(rgroups.data(), rgroups.size() * sizeof(RoaringGroup));
-  const size_t mv_tasks_off = mv_tasks.empty() ? 0 : blob.reserve(mv_tasks.size() * sizeof(MvScanTask));
-  const size_t sm_tasks_off = sm_tasks.empty() ? 0 : blob.reserve(sm_tasks.size() * sizeof(StrMatchTask));
+  P.tasks_off = P.tasks.empty() ? 0 : blob.add(P.tasks.data(), P.tasks.size() * sizeof(RoaringTask));
+  P.rgroups_off = rgroups.empty() ? 0 : blob.add(rgroups.data(), rgroups.size() * sizeof(RoaringGroup));
+  P.num_rgroups = rgroups.size();
+  P.mv_tasks_off = mv_tasks.empty() ? 0 : blob.reserve(mv_tasks.size() * sizeof(MvScanTask));
+  P.num_mv_tasks = mv_tasks.size();
+  P.mv_total_tiles = (int32_t)mv_tiles;
+  P.sm_tasks_off = sm_tasks.empty() ? 0 : blob.reserve(sm_tasks.size() * sizeof(StrMatchTask));
+  P.num_sm_tasks = sm_tasks.size();
+  P.sm_total_tiles = (int32_t)sm_tiles;
+  return PHIP_OK;
+}
 
-  // ---- filter kernel configuration (filter.hip) -------------------------------------------------
-  // Per 2048-doc tile, the wave's ring slot receives the fixed-bit words of every scanned filter column
-  // (256*b bytes) and the dense words of inverted leaves (256 bytes), each padded by kStagePad bytes on
-  // both sides (window_at reads one word before / after). Value / group-by columns are not staged:
-  // the aggregation kernel reads them for matched docs only.
-  bool has_filter = false;
-  for (const DevSeg &ds : dsegs) has_filter |= ds.node_end > ds.node_begin;
-  bool need_agg = group_by || nprog > 1;  // several programs: every COUNT is per program, in the aggregation walk
-  for (int a = 0; a < naggs; a++) need_agg |= dq.aggs[a].acc != ACC_COUNT;
-  const int ndist = (int)P.dist_agg.size();  // (the distinct pass reads the tile masks as the aggregation walk does)
-  bool need_mask = has_filter && (need_agg || want_bitmap || nsel > 0 || ndist > 0);
-  const int64_t kSlotBudget = 19 * 1024;  // bytes per ring slot
-  int32_t stage_stride = 0;
-  std::vector<double> seg_est(dsegs.size(), 1.0);
-  std::vector<int32_t> seg_off(dsegs.size(), 0);
-  for (DevSeg &ds : dsegs) {
+// ---- filter kernel configuration (filter.hip) -------------------------------------------------
+// Per 2048-doc tile, the wave's ring slot receives the fixed-bit words of every scanned filter column
+// (256*b bytes) and the dense words of inverted leaves (256 bytes), each padded by kStagePad bytes on
+// both sides (window_at reads one word before / after). Value / group-by columns are not staged:
+// the aggregation kernel reads them for matched docs only.
+// This phase: what the plan needs from the filter launch, each entry's staged regions and the path its program takes
+// (bit-sliced / conjunctive / contiguous / general), and the group-by records its selectivity estimate pays for.
+int32_t PlanBuilder::configure_filter_paths() {
+  for (const DevSeg &ds : P.dsegs) P.has_filter |= ds.node_end > ds.node_begin;
+  P.need_agg = P.group_by || P.nprog > 1;  // several programs: every COUNT is per program, in the aggregation walk
+  for (int a = 0; a < P.naggs; a++) P.need_agg |= P.dq.aggs[a].acc != ACC_COUNT;
+  // (the distinct pass reads the tile masks as the aggregation walk does)
+  P.need_mask = P.has_filter && (P.need_agg || P.want_bitmap || P.nsel > 0 || P.ndist > 0);
+  seg_est.assign(P.dsegs.size(), 1.0);
+  seg_off.assign(P.dsegs.size(), 0);
+  for (DevSeg &ds : P.dsegs) {
     int32_t off = 0;
     ds.num_stage = 0;
     ds.num_dma = 0;
@@ -4595,7 +4705,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (ds.conj_range && ds.conj_lo > ds.conj_hi) ok = false;  // (empty: the host pruned the segment already)
     if (ok && (int)conj.size() <= kMaxConj) {
       ds.conj_path = 1;
-      seg_est[&ds - dsegs.data()] = est;
+      seg_est[&ds - P.dsegs.data()] = est;
       // most selective leaf first: the short-circuit then skips the others on more tiles (AND is
       // commutative, so the doc set is unchanged)
       std::stable_sort(conj.begin(), conj.end(),
@@ -4610,16 +4720,13 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       if (conj.empty() || conj[0].first > kConjSparseSel) ds.conj_sparse = 0;
       if (getenv("PHIP_NO_SPARSE")) ds.conj_sparse = 0;  // measurement override
       // the value is the per-lane passing-doc bound under which the sparse walk is taken
-      if (ds.conj_sparse) {
-        const char *sm = getenv("PHIP_SPARSE_MAX");  // measurement override
-        ds.conj_sparse = sm ? std::max(1, std::min(32, atoi(sm))) : kConjSparseMax;
-      }
+      if (ds.conj_sparse) ds.conj_sparse = std::max(1, std::min(32, env_int("PHIP_SPARSE_MAX", kConjSparseMax)));  // measurement override
       ds.conj_p = 8;
       for (size_t i = 0; i < conj.size(); i++) {
         ds.conj_leaf[i] = conj[i].second;
         while (ds.conj_p > 1 && ds.conj_p * conj[i].second.bits > 32) ds.conj_p >>= 1;
       }
-      if (const char *e = getenv("PHIP_CONJ_P")) ds.conj_p = std::min(ds.conj_p, std::max(1, atoi(e)));  // measurement override
+      ds.conj_p = std::min(ds.conj_p, std::max(1, env_int("PHIP_CONJ_P", ds.conj_p)));  // measurement override
     }
     // general programs whose leaves are all staged (or need no tile data) run in the contiguous layout
     // (filter.hip eval_filter_contig): inverted leaves become one LDS read, scan leaves one register block
@@ -4644,49 +4751,49 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       const char *ce = getenv("PHIP_CONTIG");  // measurement override: "0" keeps the lane-major interpreter
       ds.contig = c && !(ce && ce[0] == '0') ? 1 : 0;
     }
-    seg_off[&ds - dsegs.data()] = off;
+    seg_off[&ds - P.dsegs.data()] = off;
   }
   // group-by records, from each entry's estimated selectivity (build_records' touched-lines model)
   if (rec_want) {
     bool made = false;
-    for (size_t i = 0; i < dsegs.size(); i++) {
-      const int s = dsegs[i].seg_index % nseg;
-      int32_t rc = build_records(*segs[s], q, dq, dsegs[i], colidx[s], rec_min_fields, seg_est[i], st, &made);
+    for (size_t i = 0; i < P.dsegs.size(); i++) {
+      const int s = P.dsegs[i].seg_index % P.nseg;
+      int32_t rc = build_records(*segp[s], q, P.dq, P.dsegs[i], colidx[s], rec_min_fields, seg_est[i], st, &made);
       if (rc) return rc;
     }
     if (made) HIP_TRY(hipStreamSynchronize(st));
     // A few record segments do not pay for the record variant's larger kernel on all the others (Q3.1: records on
     // its sparse edge segments only ran 0.47 -> 0.52 ms, profiles/r06zj_trace.log): records for most docs, or none.
     int64_t rec_docs = 0, all_docs = 0;
-    for (const DevSeg &d : dsegs) {
+    for (const DevSeg &d : P.dsegs) {
       all_docs += d.num_docs;
       rec_docs += d.rec != nullptr ? d.num_docs : 0;
     }
     if (rec_min_fields > 1 && 2 * rec_docs < all_docs)
-      for (DevSeg &d : dsegs) d.rec = nullptr;
+      for (DevSeg &d : P.dsegs) d.rec = nullptr;
   }
+  return PHIP_OK;
+}
+
+// Which kernel filters and aggregates: the fused aggregation (and its value columns' streaming, the small scan's
+// shape), the fused group-by and its table's placement, the lean instantiation; then the bytes the statistics report.
+int32_t PlanBuilder::configure_fusion() {
   // PHIP_GRID_CUS=n (n >= 1; tests): the CU count every tile-walking launch sizes its grid from, so that a small
   // input runs the walks with few, long-lived waves (many tiles and segment changes per wave, as at production
   // sizes). Which kernel variant or walk runs keeps following the device's CU count.
-  int grid_cus = dev->num_cus;
-  if (const char *gc = getenv("PHIP_GRID_CUS")) {
-    if (atoi(gc) >= 1) {
-      grid_cus = atoi(gc);
-      P.sel_max_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * 8);  // (8 workgroups per CU, as the XCD walks' floor)
-    }
+  grid_cus = P.dev->num_cus;
+  if (env_int("PHIP_GRID_CUS", 0) >= 1) {
+    grid_cus = env_int("PHIP_GRID_CUS", 0);
+    P.sel_max_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * 8);  // (8 workgroups per CU, as the XCD walks' floor)
   }
+  P.mv_max_blocks = std::max(1, grid_cus * 8);
   // Fused aggregation (filter.hip fused_tile): every segment on the conjunctive path, aggregation only
   // (no group-by, no HLL), at most 4 slots, a filter to fuse into. Value columns are then streamed with
   // the tile (one more LDS-DMA region) when the expected matches per 128-byte line of the column reach
   // kStreamValueMin -- a dense gather would touch every line anyway -- else gathered for matched docs.
-  bool conj_all = true;
-  for (const DevSeg &ds : dsegs) conj_all &= ds.conj_path != 0;
-  bool any_filter_prog = false;
-  for (const DevSeg &ds : dsegs) any_filter_prog |= ds.node_end > ds.node_begin;
-  int fused_naggs = 0;
-  bool any_defer = false;
-  FusedShape small_shape = {-1, 0, 0, 0, 0};  // mode >= 0: the small fused scan's shape (fused_shape.h)
-  std::vector<bool> ids_streamed((size_t)nseg * ncols, false);  // (segment, column): fused tiles stream its ids
+  for (const DevSeg &ds : P.dsegs) conj_all &= ds.conj_path != 0;
+  for (const DevSeg &ds : P.dsegs) any_filter_prog |= ds.node_end > ds.node_begin;
+  ids_streamed.assign((size_t)P.nseg * ncols, false);
   {
     // Fusion saves a launch, the mask round trip and the filter columns' re-read, but a streaming filter
     // wave that stops for a tile's projection gathers leaves its LDS-DMA ring idle. Measured on SSB SF100
@@ -4701,8 +4808,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     const char *fe = getenv("PHIP_FUSE");  // measurement override: "0" never, "1" always, unset = by size
     const int64_t kFuseMaxTiles = 8192;
     double est_docs = 0.0;
-    for (size_t i = 0; i < dsegs.size(); i++) est_docs += seg_est[i] * dsegs[i].num_docs;
-    const double per_tile = est_docs / (double)std::max<int64_t>(1, total_work);
+    for (size_t i = 0; i < P.dsegs.size(); i++) est_docs += seg_est[i] * P.dsegs[i].num_docs;
+    const double per_tile = est_docs / (double)std::max<int64_t>(1, P.total_work);
     double fuse_per_tile = 0.0;
     if (const char *fp = getenv("PHIP_FUSE_PER_TILE")) fuse_per_tile = atof(fp);  // measurement override
     // Large scans fuse too since the bit-sliced conjunction (round 3): its light evaluation leaves the wave time to
@@ -4710,27 +4817,26 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     // Q1.1 / Q1.2 / Q1.3 p50 0.64 / 0.476 / 0.487 -> 0.62 / 0.385 / 0.476 ms, sorted Q1.1 unchanged
     // (profiles/r03n_fuse_large_ab.log). Their value columns are gathered, not streamed with every tile (streaming
     // LO_EXTENDEDPRICE over 293K tiles: 1.4 ms). PHIP_FUSE_LARGE=0 restores the size rule alone.
-    const bool big = total_work > kFuseMaxTiles;
+    const bool big = P.total_work > kFuseMaxTiles;
     // A small query whose tiles are mostly matched (estimated >= kFuseDenseSplit docs per 2048-doc tile) splits: the
     // aggregation kernel's dense-tile walk projects a tile's matched docs four groups per gather round trip, where the
     // fused tile drains them through its deferred ring 128 at a time, one round trip each (C1 on 10M rows,
     // profiles/r06d_c1_ab.log: FILTERED_QUERY, 88 % matched, p50 0.199 -> 0.113 ms split).
     const double kFuseDenseSplit = 1024.0;
     const bool dense_small = !big && per_tile >= kFuseDenseSplit;
-    const char *fl = getenv("PHIP_FUSE_LARGE");  // measurement override
     bool bs_all = true;  // (the P-layout conjunction's heavier evaluation keeps the size rule)
-    for (const DevSeg &ds : dsegs) bs_all &= ds.conj == 0 || ds.conj_bs != 0;
-    const bool fuse_large = (fl ? atoi(fl) != 0 : true) && bs_all;
+    for (const DevSeg &ds : P.dsegs) bs_all &= ds.conj == 0 || ds.conj_bs != 0;
+    const bool fuse_large = env_int("PHIP_FUSE_LARGE", 1) != 0 && bs_all;  // measurement override
     // (a DISTINCTCOUNT plan takes the unfused route: its pass needs the tile masks)
-    bool fuse = conj_all && any_filter_prog && !group_by && nprog == 1 && nhll == 0 && naggs > 0 && naggs <= 4 && !want_bitmap &&
-                ndist == 0 &&
+    bool fuse = conj_all && any_filter_prog && !P.group_by && P.nprog == 1 && P.nhll == 0 && P.naggs > 0 && P.naggs <= 4 && !P.want_bitmap &&
+                P.ndist == 0 &&
                 (fe ? atoi(fe) != 0 : (!dense_small && (!big || fuse_large || (fuse_per_tile > 0 && per_tile <= fuse_per_tile))));
     bool any_value = false;
-    for (int a = 0; a < naggs; a++) any_value |= dq.aggs[a].acc != ACC_COUNT;
+    for (int a = 0; a < P.naggs; a++) any_value |= P.dq.aggs[a].acc != ACC_COUNT;
     if (fuse && any_value) {
-      fused_naggs = naggs;
+      P.fused_naggs = P.naggs;
       const char *sv_env = getenv("PHIP_STREAM_VALUES");  // measurement override: "0" never, "1" always
-      const char *sp = getenv("PHIP_STREAM_PACKED");  // measurement override: "0" = stream ids + dictionary instead
+      const bool stream_packed = !env_off("PHIP_STREAM_PACKED");  // measurement override: "0" = stream ids + dictionary instead
       const double kStreamValueMin = 0.5;
       // One pass over the segments under a streaming rule (sv: the override's form, null = the density rule): which
       // value columns join the tile's ring slot, and the slot that results. It writes the segments it is given, so the
@@ -4743,15 +4849,15 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       };
       auto lay_out = [&](const char *sv) {
         FusedLayout L;
-        L.segs = dsegs;
+        L.segs = P.dsegs;
         L.ids = ids_streamed;
         L.stride = stage_stride;
         for (size_t i = 0; i < L.segs.size(); i++) {
           DevSeg &ds = L.segs[i];
           int32_t off = seg_off[i];
           const int32_t nstage0 = ds.num_stage;
-          for (int a = 0; a < naggs; a++) {
-            const DevAgg &ag = dq.aggs[a];
+          for (int a = 0; a < P.naggs; a++) {
+            const DevAgg &ag = P.dq.aggs[a];
             if (ag.acc == ACC_COUNT) continue;
             for (int c : {ag.col_a, ag.expr != PHIP_EXPR_COLUMN ? ag.col_b : -1}) {
               if (c < 0) continue;
@@ -4759,12 +4865,12 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
               if (dc.lds_off >= 0) continue;
               // a column read through its doc-order values (as_raw) streams its packed ids instead when the tiles are
               // dense enough: fewer bytes per tile than the values, and no per-doc load at all
-              const int sidx = ds.seg_index % nseg;
-              const ColumnStore &cs = segs[sidx]->cols[colidx[sidx][c]];
+              const int sidx = ds.seg_index % P.nseg;
+              const ColumnStore &cs = segp[sidx]->cols[colidx[sidx][c]];
               const bool via_vals = !dc.has_dict && !no_dict(cs);
               if (!dc.has_dict && !via_vals) continue;
               // packed values stream as they are (vbits per doc, no dictionary gather after): fused_i64_u / fused_f64_u
-              const bool via_packed = via_vals && dc.vpack != nullptr && !(sp && atoi(sp) == 0);
+              const bool via_packed = via_vals && dc.vpack != nullptr && stream_packed;
               const int32_t bits = via_packed ? dc.vbits : via_vals ? cs.bits : dc.bits;
               const bool dense = seg_est[i] * (1024.0 / std::max(1, bits)) >= kStreamValueMin;
               if (!(sv ? atoi(sv) != 0 : (dense && !big))) continue;
@@ -4789,7 +4895,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
           L.any_streamed |= ds.num_stage != nstage0;
           // nothing streamed with the tile: the matched docs collect across tiles (filter.hip fused_defer)
           ds.fused_defer = ds.num_stage == nstage0 ? 1 : 0;
-          if (const char *fd = getenv("PHIP_FUSED_DEFER")) ds.fused_defer = ds.fused_defer && atoi(fd) != 0;  // A/B
+          ds.fused_defer = ds.fused_defer && env_int("PHIP_FUSED_DEFER", 1) != 0;  // A/B
           L.any_defer |= ds.fused_defer != 0;
         }
         return L;
@@ -4806,16 +4912,15 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       // the rule off as it always did. ("small fused scans".)
       // The rule sizes the XCD range walk, which every fused launch takes; a plan that PHIP_FILTER_WALK forces onto
       // another walk keeps the older rule below (one workgroup per CU), the shape its tests pin.
-      const char *fs = getenv("PHIP_FUSED_SMALL");
       const char *fw = getenv("PHIP_FILTER_WALK");
-      if (!getenv("PHIP_FILTER_BPC") && !(fs && atoi(fs) == 0) && (!fw || !strcmp(fw, "xcdc")) && total_work > 0 &&
-          total_work <= (int64_t)dev->num_cus * kFilterWaves * 8) {
+      if (!getenv("PHIP_FILTER_BPC") && !env_off("PHIP_FUSED_SMALL") && (!fw || !strcmp(fw, "xcdc")) && P.total_work > 0 &&
+          P.total_work <= (int64_t)P.dev->num_cus * kFilterWaves * 8) {
         auto ring_of = [](const FusedLayout &l) {
           return kFilterWaves * (l.any_defer ? 4 * kFusedRingDefer : 2 * kFusedRingTile);
         };
         FusedShapeIn in;
         memset(&in, 0, sizeof(in));
-        in.tiles = total_work;
+        in.tiles = P.total_work;
         in.slot[0] = (int32_t)round_up(std::max(lay.stride, 16), 16);
         in.doc_ring[0] = ring_of(lay);
         FusedLayout alt;
@@ -4836,7 +4941,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
                   small_shape.mode, small_shape.blocks, small_shape.nbuf, small_shape.bpc, (long long)small_shape.T);
         if (small_shape.mode == 1) lay = std::move(alt);
       }
-      dsegs = std::move(lay.segs);
+      P.dsegs = std::move(lay.segs);
       ids_streamed = std::move(lay.ids);
       stage_stride = lay.stride;
       any_defer |= lay.any_defer;
@@ -4859,35 +4964,31 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // beside the filter's rings leaves 1-3 workgroups (4-12 waves) per CU for a walk that is latency-bound, so it
   // measured slower than the separate aggregation kernel's LDS tables everywhere but Q4.1 (2.8 KB table): Q2.1 0.570 ->
   // 0.985 ms, Q3.1 0.955 -> 1.670, Q4.2 0.628 -> 1.323, Q4.1 0.780 -> 0.765 (profiles/r05t_lds_ab.log) -- opt-in only.
-  bool fused_gb = false, gb_xcd = false, gb_lds = false;
-  int64_t gb_lds_bytes = 0;  // the fused LDS table per workgroup
-  if (group_by && dq.mode != GB_HASH && conj_all && any_filter_prog && nprog == 1 && !want_bitmap && nsel == 0 &&
-      ndist == 0) {
-    const char *fg = getenv("PHIP_FUSED_GB");
-    const int fgm = fg ? atoi(fg) : 1;
-    const int64_t m = nhll ? ((int64_t)1 << log2m) : 0;
-    const int64_t table_bytes = (int64_t)(1 + naggs) * dq.num_groups * 8 + (int64_t)nhll * dq.num_groups * m;
+  if (P.group_by && P.dq.mode != GB_HASH && conj_all && any_filter_prog && P.nprog == 1 && !P.want_bitmap && P.nsel == 0 &&
+      P.ndist == 0) {
+    const int fgm = env_int("PHIP_FUSED_GB", 1);
+    const int64_t m = P.nhll ? ((int64_t)1 << P.log2m) : 0;
+    const int64_t table_bytes = (int64_t)(1 + P.naggs) * P.dq.num_groups * 8 + (int64_t)P.nhll * P.dq.num_groups * m;
     const char *force = getenv("PHIP_GB_MODE");
     const bool lds_sized = table_bytes <= 128 * 1024 && !(force && !strcmp(force, "global"));
     double est_docs = 0.0;
-    for (size_t i = 0; i < dsegs.size(); i++) est_docs += seg_est[i] * dsegs[i].num_docs;
-    const double per_key = est_docs / (double)std::max<int64_t>(1, dq.num_groups);
+    for (size_t i = 0; i < P.dsegs.size(); i++) est_docs += seg_est[i] * P.dsegs[i].num_docs;
+    const double per_key = est_docs / (double)std::max<int64_t>(1, P.dq.num_groups);
     const double kFuseGbMaxPerKey = 40.0;
-    const char *fx = getenv("PHIP_FUSED_GB_XCD_MAX");
-    const int64_t xcd_max = fx ? atoll(fx) : (int64_t)16 << 20;
+    const int64_t xcd_max = env_i64("PHIP_FUSED_GB_XCD_MAX", (int64_t)16 << 20);
     // A sorted group-by column hands each XCD's contiguous doc range a few keys at a time, so the per-key estimate
     // (uniform keys) understates how hot its rows run: SSB Q2.3 over the layout sorted by date (D_YEAR a key) 0.454 ->
     // 0.499 ms fused with XCD copies, against 0.457 -> 0.354 unsorted (profiles/r05w_sorted_ab.log).
     bool sorted_key = false;
     for (int k = 0; k < q->num_group_by; k++)
-      for (int s2 = 0; s2 < nseg; s2++)
-        sorted_key |= !segs[s2]->cols[colidx[s2][q->group_by_columns[k]]].sorted_pairs.empty();
+      for (int s2 = 0; s2 < P.nseg; s2++)
+        sorted_key |= !segp[s2]->cols[colidx[s2][q->group_by_columns[k]]].sorted_pairs.empty();
     fused_gb = fgm == 2 || fgm == 3 || (fgm == 1 && (!lds_sized || (per_key <= kFuseGbMaxPerKey && !sorted_key)));
     gb_xcd = fused_gb && fgm != 2 && table_bytes <= xcd_max && (fgm == 3 || per_key >= 1.0) &&
-             dev->num_xcc <= kXcdCopies;  // (XCC ids distinct mod kXcdCopies: device_xcc_count)
+             P.dev->num_xcc <= kXcdCopies;  // (XCC ids distinct mod kXcdCopies: device_xcc_count)
     if (fgm == 4 && lds_sized) {
       // (u64 rows, then the HLL registers packed four u8 to a u32 word: nhll x G x m bytes)
-      const int64_t lb = round_up((int64_t)(1 + naggs) * dq.num_groups * 8 + (int64_t)nhll * dq.num_groups * m, 16);
+      const int64_t lb = round_up((int64_t)(1 + P.naggs) * P.dq.num_groups * 8 + (int64_t)P.nhll * P.dq.num_groups * m, 16);
       const int64_t ss = round_up(std::max(stage_stride, 16), 16);
       if ((160 * 1024 - 256 - (int64_t)kFilterWaves * 4 * kFusedRingGB - lb) / ((int64_t)kFilterWaves * ss) >= 2) {
         fused_gb = gb_lds = true;
@@ -4897,11 +4998,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     }
     if (fused_gb) {
       any_defer = true;
-      for (DevSeg &ds : dsegs) ds.fused_defer = 1;
+      for (DevSeg &ds : P.dsegs) ds.fused_defer = 1;
     }
   }
   stage_stride = (int32_t)round_up(std::max(stage_stride, 16), 16);
-  for (const DevSeg &ds : dsegs) {
+  for (const DevSeg &ds : P.dsegs) {
     int64_t per_tile = 0;
     std::vector<int> seen;
     for (int i = ds.node_begin; i < ds.node_end; i++) {
@@ -4918,9 +5019,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
         per_tile += (int64_t)kTileDocs * type_width(ds.cols[dn.column].type);
       } else if (dn.leaf_kind == PHIP_LEAF_RAW_STRING_RANGE || dn.leaf_kind == PHIP_LEAF_RAW_STRING_SET) {
         // the doc offsets + the values' bytes (this segment's mean length)
-        const int s = ds.seg_index % nseg;
-        const ColumnStore &cs = segs[s]->cols[colidx[s][dn.column]];
-        per_tile += (int64_t)kTileDocs * 8 + (int64_t)(kTileDocs * cs.str_total / std::max<int64_t>(segs[s]->num_docs, 1));
+        const int s = ds.seg_index % P.nseg;
+        const ColumnStore &cs = segp[s]->cols[colidx[s][dn.column]];
+        per_tile += (int64_t)kTileDocs * 8 + (int64_t)(kTileDocs * cs.str_total / std::max<int64_t>(segp[s]->num_docs, 1));
       }
     }
     P.filter_bytes += per_tile * ds.num_work;
@@ -4929,8 +5030,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     if (!projected[c]) continue;
     Plan::ProjCol pc;
     pc.progs = proj_progs[c];
-    for (int s = 0; s < nseg; s++) {
-      const ColumnStore &cs = segs[s]->cols[colidx[s][c]];
+    for (int s = 0; s < P.nseg; s++) {
+      const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
       const bool raw = (as_raw(s, c) && !ids_streamed[(size_t)s * ncols + c]) || hll_doc_used[(size_t)s * ncols + c];
       // (packed doc-order values: vbits per doc and no dictionary)
       const bool packed = raw && !no_dict(cs) && !hll_doc_used[(size_t)s * ncols + c] && packed_vals(cs);
@@ -4940,28 +5041,30 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     }
     P.proj.push_back(pc);
   }
-  for (int s = 0; s < nseg; s++) P.seg_docs.push_back(segs[s]->num_docs);
-  const bool conj_only = conj_all;
-  if (fused_naggs > 0 || fused_gb) need_mask = false;  // the filter kernel aggregates its own tiles
-  const bool fused_any = fused_naggs > 0 || fused_gb;
+  for (int s = 0; s < P.nseg; s++) P.seg_docs.push_back(segp[s]->num_docs);
+  if (fused_any()) P.need_mask = false;  // the filter kernel aggregates its own tiles
   // The lean fused instantiation (filter_kernel.h kBsDefer) when the whole launch has its shape: a fused aggregation
   // whose segments all evaluate the bit-sliced conjunction (or none: conj == 0 with the doc-range cut) and all defer
   // their projection. It compiles out the P-layout conjunction and the per-tile streamed projection, which cost the
   // general instantiation 16 VGPR / 149 SGPR spills on the headline. Then no segment stages more than
   // its conjunction's planes (<= kMaxConj regions, the lean cursor's size). PHIP_FUSED_LEAN=0 keeps the general
   // instantiation (A/B).
-  bool fused_lean = fused_naggs > 0 && !fused_gb && conj_only;
-  for (const DevSeg &ds : dsegs)
+  fused_lean = P.fused_naggs > 0 && !fused_gb && conj_all;
+  for (const DevSeg &ds : P.dsegs)
     fused_lean = fused_lean && (ds.conj == 0 || ds.conj_bs != 0) && ds.fused_defer == 1 && ds.num_stage <= kMaxConj;
-  if (const char *le = getenv("PHIP_FUSED_LEAN")) fused_lean = fused_lean && atoi(le) != 0;
+  fused_lean = fused_lean && env_int("PHIP_FUSED_LEAN", 1) != 0;
+  return PHIP_OK;
+}
+
+// The filter launch: ring depth and workgroups per CU, the walk, the grid and its LDS.
+int32_t PlanBuilder::configure_filter_launch() {
   // ring depth: prefer 4 workgroups (16 waves) per CU for the VALU/LDS work of the leaves, and give
   // each wave the deepest ring that then fits the 160 KiB LDS (bytes in flight per CU =
   // blocks x 4 waves x (nbuf-1) x slot)
-  int nbuf = 0, fbpc = 0;
-  const int32_t fring_bytes = fused_gb ? 4 * kFusedRingGB : (any_defer ? 4 * kFusedRingDefer : 2 * kFusedRingTile);  // per wave
+  fring_bytes = fused_gb ? 4 * kFusedRingGB : (any_defer ? 4 * kFusedRingDefer : 2 * kFusedRingTile);  // per wave
   {
     const char *env = getenv("PHIP_FILTER_BPC");  // measurement override
-    int want = env ? std::max(1, std::min(8, atoi(env))) : (conj_only ? 6 : 4);
+    int want = env ? std::max(1, std::min(8, atoi(env))) : (conj_all ? 6 : 4);
     // A mid-sized scan (a few tiles per wave at the default) streams better with fewer, longer-lived waves and a
     // deeper ring: each wave's ring prologue is paid once per range. Measured on SSB SF100 sorted Q1.1 (42K
     // tiles): 6 -> 3 workgroups per CU, filter 0.074 -> 0.065 ms; the unsorted layout (293K tiles, 48 per wave)
@@ -4970,9 +5073,9 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     const int64_t waves_at = (int64_t)grid_cus * want * kFilterWaves;
     // (a fused launch keeps the full width: its waves also wait on gathers -- sorted Q1.1 fused 0.201 -> 0.187 ms at
     // 6 instead of 3 workgroups per CU, profiles/r03p_fused_bpc_ab.log)
-    if (!env && total_work >= 4 * waves_at && !fused_any)
-      while (want > 2 && total_work < kMinTilesPerWave * (int64_t)grid_cus * want * kFilterWaves) want--;
-    const int64_t fring = (fused_any ? (int64_t)kFilterWaves * fring_bytes : 0) + gb_lds_bytes;  // fused doc rings (+ table)
+    if (!env && P.total_work >= 4 * waves_at && !fused_any())
+      while (want > 2 && P.total_work < kMinTilesPerWave * (int64_t)grid_cus * want * kFilterWaves) want--;
+    const int64_t fring = (fused_any() ? (int64_t)kFilterWaves * fring_bytes : 0) + gb_lds_bytes;  // fused doc rings (+ table)
     const int64_t static_lds = fused_gb ? 256 : kFilterStaticLds;  // (the fused group-by holds no record rows)
     for (int bpc = want; bpc >= 1 && nbuf < 2; bpc--) {
       // a workgroup's share of the CU's 160 KiB, less the kernel's static LDS (block partials, the record mode's rows)
@@ -4990,9 +5093,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     // time every wave ended with same-address atomics (profiles/r05d_q1_small.log); fused aggregations have left it
     // for the residency rule (small_shape, above) except under a forced walk, the fused group-by has not been
     // re-measured. PHIP_FUSED_SMALL=0 keeps the width rule.
-    const char *fs = getenv("PHIP_FUSED_SMALL");
-    if (!env && fused_any && small_shape.mode < 0 && !(fs && atoi(fs) == 0) &&
-        total_work <= (int64_t)dev->num_cus * kFilterWaves * 8 && fbpc > 1) {
+    if (!env && fused_any() && small_shape.mode < 0 && !env_off("PHIP_FUSED_SMALL") &&
+        P.total_work <= (int64_t)P.dev->num_cus * kFilterWaves * 8 && fbpc > 1) {
       const int64_t nb = std::min<int64_t>(kMaxRing, ((160 * 1024) - static_lds - fring) / ((int64_t)kFilterWaves * stage_stride));
       if (nb >= 2) {
         nbuf = (int)nb;
@@ -5012,49 +5114,53 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       nbuf = fn;
     }
   }
-  const size_t filter_lds = (size_t)kFilterWaves * nbuf * stage_stride + (fused_any ? (size_t)kFilterWaves * fring_bytes : 0) +
+  P.filter_lds = (size_t)kFilterWaves * nbuf * stage_stride + (fused_any() ? (size_t)kFilterWaves * fring_bytes : 0) +
                             (size_t)gb_lds_bytes;
   const char *walk_env = getenv("PHIP_FILTER_WALK");  // measurement override: "xcd" / "xcdc" / "contig"
   // contiguous per-wave ranges measured fastest for the plain filter; a fused aggregation's waves stay inside
   // their XCD's eighth of the work (its dictionaries then stay in that XCD's L2)
-  int xcd_walk = fused_any ? 2 : 0;
+  xcd_walk = fused_any() ? 2 : 0;
   if (walk_env) xcd_walk = !strcmp(walk_env, "xcd") ? 1 : (!strcmp(walk_env, "xcdc") ? 2 : 0);
-  int64_t min_tiles_per_wave = 1;
-  if (const char *mt = getenv("PHIP_FILTER_MIN_TILES")) min_tiles_per_wave = std::max(1, atoi(mt));  // A/B
-  int filter_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)grid_cus * fbpc,
-                                                                  ceil_div(total_work, kFilterWaves * min_tiles_per_wave)));
+  const int64_t min_tiles_per_wave = std::max(1, env_int("PHIP_FILTER_MIN_TILES", 1));  // A/B
+  P.filter_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)grid_cus * fbpc,
+                                                                  ceil_div(P.total_work, kFilterWaves * min_tiles_per_wave)));
   // (the small fused scan: the workgroups of its shape -- all resident; a device's CU count times any workgroups per CU
   // is a multiple of 8, so the XCD walk's rounding keeps them so)
-  if (small_shape.mode >= 0) filter_blocks = small_shape.blocks;
-  if (xcd_walk) filter_blocks = (int)round_up(std::max(filter_blocks, 8), 8);
+  if (small_shape.mode >= 0) P.filter_blocks = small_shape.blocks;
+  if (xcd_walk) P.filter_blocks = (int)round_up(std::max(P.filter_blocks, 8), 8);
+  return PHIP_OK;
+}
 
-  // ---- aggregation kernel configuration (aggregate.hip) -----------------------------------------
-  dq.log2m = log2m;
-  if (dq.mode != GB_HASH) dq.mode = group_by ? GB_GLOBAL : GB_NONE;
-  if (group_by) dq.dense_batch = 0;  // (set below for GB_LDS: the batched group-by walk)
-  const int m_regs = nhll ? (1 << log2m) : 0;
-  size_t agg_lds = (size_t)kAggWaves * ring_entries(dq.mode) * 4 + (size_t)kAggWaves * dq.stage_bytes;
+// ---- aggregation kernel configuration (aggregate.hip) -----------------------------------------
+// The group table's mode (GB_NONE / GB_GLOBAL / GB_LDS / GB_HASH), the GB_LDS walks, the id histogram's LDS, the grid.
+int32_t PlanBuilder::configure_aggregation() {
+  P.dq.log2m = P.log2m;
+  if (P.dq.mode != GB_HASH) P.dq.mode = P.group_by ? GB_GLOBAL : GB_NONE;
+  if (P.group_by) P.dq.dense_batch = 0;  // (set below for GB_LDS: the batched group-by walk)
+  P.m_regs = P.nhll ? (1 << P.log2m) : 0;
+  P.agg_lds = (size_t)kAggWaves * ring_entries(P.dq.mode) * 4 + (size_t)kAggWaves * P.dq.stage_bytes;
   int agg_bpc = 4;
-  void *first_doc = nullptr;
-  if (group_by && dq.mode == GB_HASH && nseg == 1 && gb_key_space >= q->num_groups_limit && q->num_groups_limit > 0) {
-    int32_t rc0 = P.alloc((size_t)dq.num_groups * 4, &first_doc);
+  if (P.group_by && P.dq.mode == GB_HASH && P.nseg == 1 && gb_key_space >= q->num_groups_limit && q->num_groups_limit > 0) {
+    void *fd = nullptr;
+    int32_t rc0 = P.alloc((size_t)P.dq.num_groups * 4, &fd);
     if (rc0) return rc0;
-    dq.seg_keys = 1;
-    dq.seg_key_mult = 1;
-    dq.first_doc = (uint32_t *)first_doc;
+    P.first_doc = (uint32_t *)fd;
+    P.dq.seg_keys = 1;
+    P.dq.seg_key_mult = 1;
+    P.dq.first_doc = P.first_doc;
   }
-  if (group_by && dq.mode == GB_HASH) {
-    if ((int64_t)nhll * dq.num_groups * m_regs * 4 > ((int64_t)16 << 30))
+  if (P.group_by && P.dq.mode == GB_HASH) {
+    if ((int64_t)P.nhll * P.dq.num_groups * P.m_regs * 4 > ((int64_t)16 << 30))
       return fail(PHIP_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL registers of %lld hash slots exceed the memory budget",
-                  (long long)dq.num_groups);
-  } else if (group_by) {
-    const int64_t tbl_words = (int64_t)(1 + naggs) * dq.num_groups;
-    const int64_t hll_words = (int64_t)nhll * dq.num_groups * m_regs / 4;
+                  (long long)P.dq.num_groups);
+  } else if (P.group_by) {
+    const int64_t tbl_words = (int64_t)(1 + P.naggs) * P.dq.num_groups;
+    const int64_t hll_words = (int64_t)P.nhll * P.dq.num_groups * P.m_regs / 4;
     const int64_t table_bytes = tbl_words * 8 + hll_words * 4;
     const char *force = getenv("PHIP_GB_MODE");  // measurement override: "lds" / "global"
     bool use_lds = table_bytes <= 128 * 1024 && (!fused_gb || gb_lds);
     if (force && !strcmp(force, "global")) use_lds = false;
-    if (force && !strcmp(force, "lds") && !fused_gb && (int64_t)agg_lds + round_up(table_bytes, 16) <= 159 * 1024)
+    if (force && !strcmp(force, "lds") && !fused_gb && (int64_t)P.agg_lds + round_up(table_bytes, 16) <= 159 * 1024)
       use_lds = true;
     // The batched walk (aggregate.hip group_ring_batch: kBatch chunks per gather round trip) for LDS tables, the
     // one-chunk walk for HBM tables: measured on SSB SF100 (tools/gb_ab.py, profiles/r04b_gb_ab.log) the LDS
@@ -5066,16 +5172,16 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     const int64_t tb = round_up(table_bytes, 16);
     const int64_t ring_extra = (int64_t)kAggWaves * (kRingGroupBatch - kRingGroup) * 4;
     auto bpc_of = [&](int64_t lds) { return std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024 - 1024) / lds)); };
-    bool batched = use_lds && bpc_of((int64_t)agg_lds + ring_extra + tb) >= bpc_of((int64_t)agg_lds + tb);
+    bool batched = use_lds && bpc_of((int64_t)P.agg_lds + ring_extra + tb) >= bpc_of((int64_t)P.agg_lds + tb);
     if (gbb) batched = atoi(gbb) != 0;
-    if (use_lds && (int64_t)agg_lds + ring_extra + tb > 159 * 1024) batched = false;
-    dq.dense_batch = batched ? 1 : 0;
-    agg_lds = (size_t)kAggWaves * ring_entries(dq.mode == GB_HASH ? GB_HASH : GB_LDS, batched) * 4 +
-              (size_t)kAggWaves * dq.stage_bytes;
+    if (use_lds && (int64_t)P.agg_lds + ring_extra + tb > 159 * 1024) batched = false;
+    P.dq.dense_batch = batched ? 1 : 0;
+    P.agg_lds = (size_t)kAggWaves * ring_entries(P.dq.mode == GB_HASH ? GB_HASH : GB_LDS, batched) * 4 +
+              (size_t)kAggWaves * P.dq.stage_bytes;
     if (use_lds) {
-      dq.mode = GB_LDS;
-      dq.tbl_words = (int32_t)tbl_words;
-      dq.hll_words = (int32_t)hll_words;
+      P.dq.mode = GB_LDS;
+      P.dq.tbl_words = (int32_t)tbl_words;
+      P.dq.hll_words = (int32_t)hll_words;
       // A table that leaves one 8-wave workgroup per CU (Q2.1's 7000 groups x 16 B = 112 KB): 16-wave workgroups share
       // it, so the CU keeps 16 waves of gathers in flight instead of 8 (SQ: the 8-wave walk spent 76 % of its wave
       // cycles in s_waitcnt, profiles/r05l_sq_gb.txt). Not where 8-wave workgroups already keep 16-24 waves: C5's
@@ -5085,11 +5191,11 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       auto walk_of = [&](bool b) {
         Plan::GbWalk w;
         w.batched = b;
-        w.lds = (size_t)kAggWaves * ring_entries(GB_LDS, b) * 4 + (size_t)kAggWaves * dq.stage_bytes +
+        w.lds = (size_t)kAggWaves * ring_entries(GB_LDS, b) * 4 + (size_t)kAggWaves * P.dq.stage_bytes +
                 (size_t)round_up(table_bytes, 16);
         int bpc = std::max(1, std::min(4, (int)((160 * 1024 - 1024) / w.lds)));
         w.waves = kAggWaves;
-        const size_t lds16 = (size_t)16 * ring_entries(GB_LDS, b) * 4 + (size_t)16 * dq.stage_bytes +
+        const size_t lds16 = (size_t)16 * ring_entries(GB_LDS, b) * 4 + (size_t)16 * P.dq.stage_bytes +
                              (size_t)round_up(table_bytes, 16);
         const int bpc16 = lds16 <= (size_t)159 * 1024 ? std::max(1, std::min(2, (int)((160 * 1024 - 1024) / lds16))) : 0;
         const bool want16 = gw ? atoi(gw) == 16 : bpc == 1;
@@ -5098,7 +5204,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
           w.lds = lds16;
           bpc = bpc16;
         }
-        w.blocks = (int)std::min<int64_t>((int64_t)grid_cus * bpc, ceil_div(total_work, w.waves));
+        w.blocks = (int)std::min<int64_t>((int64_t)grid_cus * bpc, ceil_div(P.total_work, w.waves));
         w.blocks = (int)round_up(std::max(w.blocks, 8), 8);  // the XCD walk needs a multiple of 8 workgroups
         w.ok = w.lds <= (size_t)159 * 1024;
         return w;
@@ -5106,8 +5212,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       P.walk[0] = walk_of(false);
       P.walk[1] = walk_of(true);
       const Plan::GbWalk &w = P.walk[batched ? 1 : 0];
-      agg_lds = w.lds;
-      dq.wg_waves = w.waves;
+      P.agg_lds = w.lds;
+      P.dq.wg_waves = w.waves;
       agg_bpc = std::max(1, (int)((w.blocks + grid_cus - 1) / grid_cus));
       // Which walk runs follows the matched docs (the one-chunk walk for sparse matches, the batched one above
       // kWalkBatchDocsPerCu per CU): the plan starts with the rule above and re-chooses after every execution.
@@ -5116,202 +5222,201 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       // 0.46M 0.065 -> 0.035. HLL tables keep the rule when they gather per column (C5 23.8M docs: batched 0.83 ms
       // vs 0.77); with group-by records the batched walk wins there too (C5 0.63 -> 0.61, profiles/r06w_rec_ab.log).
       bool any_rec = false;
-      for (const DevSeg &d : dsegs) any_rec |= d.rec != nullptr;
-      dq.rec_on = any_rec ? 1 : 0;  // (the agg_kernel variant that reads them)
-      P.walk_adaptive = (nhll == 0 || any_rec) && !gbb && !gw && !fused_gb && P.walk[0].ok && P.walk[1].ok;
+      for (const DevSeg &d : P.dsegs) any_rec |= d.rec != nullptr;
+      P.dq.rec_on = any_rec ? 1 : 0;  // (the agg_kernel variant that reads them)
+      P.walk_adaptive = (P.nhll == 0 || any_rec) && !gbb && !gw && !fused_gb && P.walk[0].ok && P.walk[1].ok;
       P.walk_cur = batched ? 1 : 0;
     }
-  } else if (nhll) {
-    agg_lds += (size_t)nhll * m_regs * 4;
+  } else if (P.nhll) {
+    P.agg_lds += (size_t)P.nhll * P.m_regs * 4;
   }
-  if (!group_by && dq.hist_aggs) agg_lds += (size_t)kAggWaves * dq.hist_words * 4;  // (the waves' id bins)
-  if (dq.wg_waves == 0) dq.wg_waves = kAggWaves;
-  if (dq.mode != GB_LDS || fused_gb) {  // only the LDS-table walks read group-by records (the segments keep theirs)
-    dq.rec_on = 0;
-    for (DevSeg &d : dsegs) d.rec = nullptr;
+  if (!P.group_by && P.dq.hist_aggs) P.agg_lds += (size_t)kAggWaves * P.dq.hist_words * 4;  // (the waves' id bins)
+  if (P.dq.wg_waves == 0) P.dq.wg_waves = kAggWaves;
+  if (P.dq.mode != GB_LDS || fused_gb) {  // only the LDS-table walks read group-by records (the segments keep theirs)
+    P.dq.rec_on = 0;
+    for (DevSeg &d : P.dsegs) d.rec = nullptr;
   }
-  int agg_blocks = (int)std::min<int64_t>((int64_t)grid_cus * agg_bpc, ceil_div(total_work, dq.wg_waves));
-  agg_blocks = (int)round_up(std::max(agg_blocks, 8), 8);  // the XCD walk needs a multiple of 8 workgroups
-  if (P.walk_cur >= 0) agg_blocks = P.walk[P.walk_cur].blocks;
+  P.agg_blocks = (int)std::min<int64_t>((int64_t)grid_cus * agg_bpc, ceil_div(P.total_work, P.dq.wg_waves));
+  P.agg_blocks = (int)round_up(std::max(P.agg_blocks, 8), 8);  // the XCD walk needs a multiple of 8 workgroups
+  if (P.walk_cur >= 0) P.agg_blocks = P.walk[P.walk_cur].blocks;
+  return PHIP_OK;
+}
 
-  const size_t nodes_off = blob.reserve(std::max<size_t>(nodes.size(), 1) * sizeof(DevNode));
-  kinds[naggs] = ACC_COUNT;
-  kinds[naggs + 1] = ACC_COUNT;
-  const size_t kinds_off = blob.add(kinds.data(), kinds.size() * 4);
-  const size_t dq_off = blob.reserve(sizeof(DevAggQuery));  // written once every pointer is known
-  const size_t sq_off = nsel > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
-  const size_t sq2_off = nord > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
-  const size_t so_off = nord > 0 ? blob.reserve(sizeof(DevSelOrder)) : 0;
-  const size_t dstq_off = ndist > 0 ? blob.reserve(sizeof(DevDistinctQuery)) : 0;
-  const size_t dr_off = sel_distinct ? blob.reserve(sizeof(DevDistinctRows)) : 0;
-  std::vector<size_t> dr_values_off(dr_values.size(), 0);
+// The blob's last reservations, its device allocation and the pointers into it, the filter descriptor, and every
+// buffer the launches write: partials, finals, masks, group tables, the distinct pass's bitmap.
+int32_t PlanBuilder::allocate() {
+  nodes_off = blob.reserve(std::max<size_t>(nodes.size(), 1) * sizeof(DevNode));
+  kinds[P.naggs] = ACC_COUNT;
+  kinds[P.naggs + 1] = ACC_COUNT;
+  P.kinds_off = blob.add(kinds.data(), kinds.size() * 4);
+  P.dq_off = blob.reserve(sizeof(DevAggQuery));  // written once every pointer is known
+  P.sq_off = P.nsel > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
+  P.sq2_off = nord > 0 ? blob.reserve(sizeof(DevSelQuery)) : 0;
+  P.so_off = nord > 0 ? blob.reserve(sizeof(DevSelOrder)) : 0;
+  P.dstq_off = P.ndist > 0 ? blob.reserve(sizeof(DevDistinctQuery)) : 0;
+  P.dr_off = P.sel_distinct ? blob.reserve(sizeof(DevDistinctRows)) : 0;
+  dr_values_off.assign(dr_values.size(), 0);
   for (size_t k = 0; k < dr_values.size(); k++)
     if (!dr_values[k].empty()) dr_values_off[k] = blob.add(dr_values[k].data(), dr_values[k].size() * 8);
 
   void *dblob;
   int32_t rc = P.alloc(blob.data.size() + 64, &dblob);
   if (rc) return rc;
-  uint8_t *base = (uint8_t *)dblob;
-  for (auto &f : aux_fix) nodes[f.node].aux = base + f.off;
+  P.base = (uint8_t *)dblob;
+  for (auto &f : aux_fix) nodes[f.node].aux = P.base + f.off;
   for (size_t i = 0; i < mv_tasks.size(); i++)
-    if (mv_set_offs[i] != SIZE_MAX) mv_tasks[i].set = (const uint32_t *)(base + mv_set_offs[i]);
-  if (!mv_tasks.empty()) memcpy(blob.data.data() + mv_tasks_off, mv_tasks.data(), mv_tasks.size() * sizeof(MvScanTask));
-  for (size_t i = 0; i < sm_tasks.size(); i++) sm_tasks[i].table = (const uint32_t *)(base + sm_table_offs[i]);
-  if (!sm_tasks.empty()) memcpy(blob.data.data() + sm_tasks_off, sm_tasks.data(), sm_tasks.size() * sizeof(StrMatchTask));
+    if (mv_set_offs[i] != SIZE_MAX) mv_tasks[i].set = (const uint32_t *)(P.base + mv_set_offs[i]);
+  if (!mv_tasks.empty()) memcpy(blob.data.data() + P.mv_tasks_off, mv_tasks.data(), mv_tasks.size() * sizeof(MvScanTask));
+  for (size_t i = 0; i < sm_tasks.size(); i++) sm_tasks[i].table = (const uint32_t *)(P.base + sm_table_offs[i]);
+  if (!sm_tasks.empty()) memcpy(blob.data.data() + P.sm_tasks_off, sm_tasks.data(), sm_tasks.size() * sizeof(StrMatchTask));
   if (!nodes.empty()) memcpy(blob.data.data() + nodes_off, nodes.data(), nodes.size() * sizeof(DevNode));
-  if (!dsegs.empty()) memcpy(blob.data.data() + segs_off, dsegs.data(), sizeof(DevSeg) * dsegs.size());
-  const DevSeg *dev_segs = (const DevSeg *)(base + segs_off);
+  if (!P.dsegs.empty()) memcpy(blob.data.data() + segs_off, P.dsegs.data(), sizeof(DevSeg) * P.dsegs.size());
+  dev_segs = (const DevSeg *)(P.base + segs_off);
 
-  DevFilter fq;
-  memset(&fq, 0, sizeof(fq));
-  fq.segs = dev_segs;
-  fq.nodes = (const DevNode *)(base + nodes_off);
-  fq.num_segs = (int32_t)dsegs.size();
-  fq.total_work = (int32_t)total_work;
-  fq.stage_stride = stage_stride;
-  fq.nbuf = nbuf;
-  fq.fring_bytes = fring_bytes;
-  fq.xcd_walk = xcd_walk;
-  {
-    const char *pe = getenv("PHIP_FILTER_PROBE");
-    fq.probe = pe ? atoi(pe) : 0;
-    // range scans of the contiguous evaluator inline: the call's register save / restore through scratch cost
-    // 4-9 % of C4's filter kernel (tools/c4_ab.py, profiles/r02f_c4_inline_ab.log); "0" = the call (A/B)
-    const char *ie = getenv("PHIP_CONTIG_INLINE");
-    fq.contig_inline = ie ? atoi(ie) : 1;
-  }
-  fq.stats_programs = q->stats_programs ? (uint32_t)q->stats_programs : 0xffffffffu;
-  {
-    const char *mn = getenv("PHIP_MASK_NT");  // measurement switch: non-temporal tile-mask stores
-    fq.mask_nt = mn ? atoi(mn) : 0;
-  }
-  fq.min_dma = 0;
-  for (size_t i = 0; i < dsegs.size(); i++)
-    fq.min_dma = i == 0 ? dsegs[i].num_dma : std::min(fq.min_dma, dsegs[i].num_dma);
-  dq.segs = dev_segs;
+  memset(&P.fq, 0, sizeof(P.fq));
+  P.fq.segs = dev_segs;
+  P.fq.nodes = (const DevNode *)(P.base + nodes_off);
+  P.fq.num_segs = (int32_t)P.dsegs.size();
+  P.fq.total_work = (int32_t)P.total_work;
+  P.fq.stage_stride = stage_stride;
+  P.fq.nbuf = nbuf;
+  P.fq.fring_bytes = fring_bytes;
+  P.fq.xcd_walk = xcd_walk;
+  P.fq.probe = env_int("PHIP_FILTER_PROBE", 0);
+  // range scans of the contiguous evaluator inline: the call's register save / restore through scratch cost
+  // 4-9 % of C4's filter kernel (tools/c4_ab.py, profiles/r02f_c4_inline_ab.log); "0" = the call (A/B)
+  P.fq.contig_inline = env_int("PHIP_CONTIG_INLINE", 1);
+  P.fq.stats_programs = q->stats_programs ? (uint32_t)q->stats_programs : 0xffffffffu;
+  P.fq.mask_nt = env_int("PHIP_MASK_NT", 0);  // measurement switch: non-temporal tile-mask stores
+  P.fq.min_dma = 0;
+  for (size_t i = 0; i < P.dsegs.size(); i++)
+    P.fq.min_dma = i == 0 ? P.dsegs[i].num_dma : std::min(P.fq.min_dma, P.dsegs[i].num_dma);
+  P.dq.segs = dev_segs;
 
-  void *fpart, *finals, *seg_matched, *apart = nullptr, *masks = nullptr;
-  rc = P.alloc((size_t)filter_blocks * 2 * 8, &fpart);
+  rc = P.alloc((size_t)P.filter_blocks * 2 * 8, &P.fpart);
   if (rc) return rc;
   // finals[64] | seg_matched[nmatch] | hll registers: the same layout as the pinned landing area, so one
   // D2H copy brings every per-execution result back
-  const int nmatch = nprog * nseg;
-  rc = P.alloc((64 + (size_t)nmatch) * 8 + (size_t)std::max(nhll, 1) * (1 << 12) * 4, &finals);
+  P.nmatch = P.nprog * P.nseg;
+  rc = P.alloc((64 + (size_t)P.nmatch) * 8 + (size_t)std::max(P.nhll, 1) * (1 << 12) * 4, &P.finals);
   if (rc) return rc;
-  seg_matched = (uint64_t *)finals + 64;
-  fq.partials = (uint64_t *)fpart;
-  fq.seg_matched = (uint64_t *)seg_matched;
+  P.seg_matched = (uint64_t *)P.finals + 64;
+  P.fq.partials = (uint64_t *)P.fpart;
+  P.fq.seg_matched = (uint64_t *)P.seg_matched;
   // finals: [0, naggs) aggregation slots, [32, 34) matched docs + entries scanned in filter
-  dq.hll_regs = (uint32_t *)((uint64_t *)finals + 64 + nmatch);
-  if (need_mask) {
-    rc = P.alloc((size_t)std::max<int64_t>(total_work, 1) * 64 * 4, &masks);
+  P.dq.hll_regs = (uint32_t *)((uint64_t *)P.finals + 64 + P.nmatch);
+  if (P.need_mask) {
+    rc = P.alloc((size_t)std::max<int64_t>(P.total_work, 1) * 64 * 4, &P.masks);
     if (rc) return rc;
-    fq.mask_out = (uint32_t *)masks;
-    dq.mask = (const uint32_t *)masks;
+    P.fq.mask_out = (uint32_t *)P.masks;
+    P.dq.mask = (const uint32_t *)P.masks;
   }
-  if (need_agg && !group_by) {
-    const int pblocks = fused_naggs > 0 ? filter_blocks : agg_blocks;
-    rc = P.alloc((size_t)pblocks * std::max(naggs, 1) * 8, &apart);
+  if (P.need_agg && !P.group_by) {
+    const int pblocks = P.fused_naggs > 0 ? P.filter_blocks : P.agg_blocks;
+    rc = P.alloc((size_t)pblocks * std::max(P.naggs, 1) * 8, &P.apart);
     if (rc) return rc;
-    dq.partials = (uint64_t *)apart;
-    if (fused_naggs > 0) {
-      fq.agg_partials = (uint64_t *)apart;
-      fq.agg = (const DevAggQuery *)(base + dq_off);
+    P.dq.partials = (uint64_t *)P.apart;
+    if (P.fused_naggs > 0) {
+      P.fq.agg_partials = (uint64_t *)P.apart;
+      P.fq.agg = (const DevAggQuery *)(P.base + P.dq_off);
     }
   }
-  if (fused_gb) fq.agg = (const DevAggQuery *)(base + dq_off);
-  void *gtab = nullptr, *ghll = nullptr, *slab = nullptr, *hslab = nullptr;
-  if (group_by) {
+  if (fused_gb) P.fq.agg = (const DevAggQuery *)(P.base + P.dq_off);
+  if (P.group_by) {
     const size_t copies = gb_xcd ? kXcdCopies : 1;
-    rc = P.alloc(copies * (1 + naggs) * dq.num_groups * 8, &gtab);
+    rc = P.alloc(copies * (1 + P.naggs) * P.dq.num_groups * 8, &P.gtab);
     if (rc) return rc;
-    if (nhll) {
-      rc = P.alloc(copies * nhll * dq.num_groups * m_regs * 4, &ghll);
+    if (P.nhll) {
+      rc = P.alloc(copies * P.nhll * P.dq.num_groups * P.m_regs * 4, &P.ghll);
       if (rc) return rc;
     }
     if (gb_xcd) {
-      dq.xcd_words = (int64_t)(1 + naggs) * dq.num_groups;
-      dq.xcd_hll_words = (int64_t)nhll * dq.num_groups * m_regs;
+      P.dq.xcd_words = (int64_t)(1 + P.naggs) * P.dq.num_groups;
+      P.dq.xcd_hll_words = (int64_t)P.nhll * P.dq.num_groups * P.m_regs;
     }
-    if (dq.mode == GB_HASH) {
+    if (P.dq.mode == GB_HASH) {
       void *hk = nullptr, *ho = nullptr;
-      rc = P.alloc((size_t)dq.num_groups * 8, &hk);
+      rc = P.alloc((size_t)P.dq.num_groups * 8, &hk);
       if (rc) return rc;
       rc = P.alloc(16, &ho);
       if (rc) return rc;
-      dq.gb_keys = (uint64_t *)hk;
-      dq.hash_overflow = (uint32_t *)ho;
+      P.dq.gb_keys = (uint64_t *)hk;
+      P.dq.hash_overflow = (uint32_t *)ho;
     }
-    if (dq.mode == GB_LDS) {
+    if (P.dq.mode == GB_LDS) {
       // (the fused LDS table: one slab per filter workgroup; an adaptive walk: the larger grid of the two)
-      const size_t nslabs = gb_lds ? filter_blocks
-                                   : std::max<int>(agg_blocks, P.walk_adaptive ? std::max(P.walk[0].blocks, P.walk[1].blocks) : 0);
-      rc = P.alloc(nslabs * dq.tbl_words * 8 + 16, &slab);
+      const size_t nslabs = gb_lds ? P.filter_blocks
+                                   : std::max<int>(P.agg_blocks, P.walk_adaptive ? std::max(P.walk[0].blocks, P.walk[1].blocks) : 0);
+      rc = P.alloc(nslabs * P.dq.tbl_words * 8 + 16, &P.slab);
       if (rc) return rc;
-      if (nhll) {
-        rc = P.alloc(nslabs * dq.hll_words * 4 + 16, &hslab);
+      if (P.nhll) {
+        rc = P.alloc(nslabs * P.dq.hll_words * 4 + 16, &P.hslab);
         if (rc) return rc;
       }
-      dq.gb_table = (uint64_t *)slab;
-      dq.gb_hll = (uint32_t *)hslab;
+      P.dq.gb_table = (uint64_t *)P.slab;
+      P.dq.gb_hll = (uint32_t *)P.hslab;
     } else {
-      dq.gb_table = (uint64_t *)gtab;
-      dq.gb_hll = (uint32_t *)ghll;
+      P.dq.gb_table = (uint64_t *)P.gtab;
+      P.dq.gb_hll = (uint32_t *)P.ghll;
     }
   }
-  void *fo = nullptr;
-  if (want_bitmap) {
-    rc = P.alloc((size_t)filter_nwords * 8 + 4096 * 8, &fo);
+  if (P.want_bitmap) {
+    rc = P.alloc((size_t)P.filter_nwords * 8 + 4096 * 8, &P.fo);
     if (rc) return rc;
   }
 
-  memcpy(blob.data.data() + dq_off, &dq, sizeof(dq));
-  if (ndist > 0) {
-    P.dist_bytes = (size_t)dstq.num_rows * (size_t)dstq.row_words * 4;
+  // the device's image of dq; the host's P.dq parts from it below (finish_completion: hist_aggs, fin)
+  memcpy(blob.data.data() + P.dq_off, &P.dq, sizeof(P.dq));
+  if (P.ndist > 0) {
+    P.dist_bytes = (size_t)P.dstq.num_rows * (size_t)P.dstq.row_words * 4;
     rc = P.alloc(P.dist_bytes, &P.dist_bits);
     if (rc) return rc;
-    dstq.segs = dev_segs;
-    dstq.num_segs = (int32_t)dsegs.size();
-    dstq.total_work = (int32_t)total_work;
-    dstq.mask = need_mask ? (const uint32_t *)masks : nullptr;
-    dstq.bitmap = (uint32_t *)P.dist_bits;
-    memcpy(blob.data.data() + dstq_off, &dstq, sizeof(dstq));
-    P.ndist = ndist;
-    P.dstq = dstq;
-    P.dstq_off = dstq_off;
-    P.dist_lds_bytes = dstq.lds ? (size_t)round_up(std::max<int64_t>(dstq.row_words, 1) * 4, 16) : 0;
+    P.dstq.segs = dev_segs;
+    P.dstq.num_segs = (int32_t)P.dsegs.size();
+    P.dstq.total_work = (int32_t)P.total_work;
+    P.dstq.mask = P.need_mask ? (const uint32_t *)P.masks : nullptr;
+    P.dstq.bitmap = (uint32_t *)P.dist_bits;
+    memcpy(blob.data.data() + P.dstq_off, &P.dstq, sizeof(P.dstq));
+    P.dist_lds_bytes = P.dstq.lds ? (size_t)round_up(std::max<int64_t>(P.dstq.row_words, 1) * 4, 16) : 0;
     // the LDS regime flushes once per workgroup: no more workgroups than stay resident; the global one spreads wider
-    P.dist_blocks = grid_cus * (dstq.lds ? 4 : 8);
+    P.dist_blocks = grid_cus * (P.dstq.lds ? 4 : 8);
     for (auto &e : P.dist_ev) HIP_TRY(hipEventCreate(&e));
   }
-  if (nsel > 0) {
+  return PHIP_OK;
+}
+
+// A selection's descriptors and scratch (the candidates' chain of an ORDER BY, the bitmap or sort buffers of a
+// DISTINCT), then the blob's one synchronous copy to the device.
+int32_t PlanBuilder::finish_selection() {
+  int32_t rc = PHIP_OK;
+  if (P.nsel > 0) {
     void *sb;
-    const size_t nent = dsegs.size();
-    rc = P.alloc(((size_t)total_work + 1) * 16 + (2 * nent + 1) * 8 + 16, &sb);
+    const size_t nent = P.dsegs.size();
+    rc = P.alloc(((size_t)P.total_work + 1) * 16 + (2 * nent + 1) * 8 + 16, &sb);
     if (rc) return rc;
     P.sel_tile_cnt = (int64_t *)sb;
-    P.sel_tile_off = P.sel_tile_cnt + total_work + 1;
-    P.sel_base = P.sel_tile_off + total_work + 1;
+    P.sel_tile_off = P.sel_tile_cnt + P.total_work + 1;
+    P.sel_base = P.sel_tile_off + P.total_work + 1;
     P.sel_kept = P.sel_base + nent + 1;
     P.sel_total = P.sel_kept + nent;
     sq.segs = dev_segs;
     sq.num_segs = (int32_t)nent;
-    sq.total_work = (int32_t)total_work;
-    sq.mask = has_filter ? (const uint32_t *)masks : nullptr;
+    sq.total_work = (int32_t)P.total_work;
+    sq.mask = P.has_filter ? (const uint32_t *)P.masks : nullptr;
     sq.tile_off = P.sel_tile_off;
     sq.seg_base = P.sel_base;
-    memcpy(blob.data.data() + sq_off, &sq, sizeof(sq));
+    memcpy(blob.data.data() + P.sq_off, &sq, sizeof(sq));
     if (nord > 0) {
       // the candidates' chain: its own tile counts, ranks and bases over the candidate masks, every candidate kept
       void *ob, *cm;
-      rc = P.alloc((size_t)kSelOrderBins * 8 + 16 + ((size_t)total_work + 1) * 16 + (2 * nent + 1) * 8 + 16, &ob);
+      rc = P.alloc((size_t)kSelOrderBins * 8 + 16 + ((size_t)P.total_work + 1) * 16 + (2 * nent + 1) * 8 + 16, &ob);
       if (rc) return rc;
-      rc = P.alloc(std::max<size_t>((size_t)total_work, 1) * 64 * 4, &cm);
+      rc = P.alloc(std::max<size_t>((size_t)P.total_work, 1) * 64 * 4, &cm);
       if (rc) return rc;
       P.sel_bins = (uint64_t *)ob;
       P.sel_tile_cnt2 = (int64_t *)(P.sel_bins + kSelOrderBins + 2);
-      P.sel_tile_off2 = P.sel_tile_cnt2 + total_work + 1;
-      P.sel_base2 = P.sel_tile_off2 + total_work + 1;
+      P.sel_tile_off2 = P.sel_tile_cnt2 + P.total_work + 1;
+      P.sel_base2 = P.sel_tile_off2 + P.total_work + 1;
       P.sel_kept2 = P.sel_base2 + nent + 1;
       P.sel_total2 = P.sel_kept2 + nent;
       so.bins = P.sel_bins;
@@ -5321,28 +5426,22 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       sq2.mask = so.cand_mask;
       sq2.tile_off = P.sel_tile_off2;
       sq2.seg_base = P.sel_base2;
-      memcpy(blob.data.data() + sq2_off, &sq2, sizeof(sq2));
-      memcpy(blob.data.data() + so_off, &so, sizeof(so));
+      memcpy(blob.data.data() + P.sq2_off, &sq2, sizeof(sq2));
+      memcpy(blob.data.data() + P.so_off, &so, sizeof(so));
       P.sel_ordered = true;
-      P.sq2_off = sq2_off;
-      P.so_off = so_off;
-      P.sel_terms = sel_terms;
       P.sel_keep = so.keep;
-      P.sel_order_cols = sel_order_cols;
-      P.sel_rest_cols = sel_rest_cols;
     }
-    if (sel_distinct) {
-      drq.segs = dev_segs;
-      drq.num_segs = (int32_t)nent;
-      drq.total_work = (int32_t)total_work;
-      drq.mask = sq.mask;
-      drq.tile_off = P.sel_tile_off;
-      if (drq.regime == DR_SORTED) {
+    if (P.sel_distinct) {
+      P.drq.segs = dev_segs;
+      P.drq.num_segs = (int32_t)nent;
+      P.drq.total_work = (int32_t)P.total_work;
+      P.drq.mask = sq.mask;
+      P.drq.tile_off = P.sel_tile_off;
+      if (P.drq.regime == DR_SORTED) {
         // one key per matched doc, at most every doc of the work list: keys, sorted, unique and the sort's scratch
         int64_t n_max = 0;
-        for (const DevSeg &ds : dsegs) n_max += std::min<int64_t>(ds.num_docs, (int64_t)ds.num_work * kTileDocs);
-        const char *sbe = getenv("PHIP_DISTINCT_ROWS_SORT_BYTES");
-        const int64_t sort_budget = sbe ? atoll(sbe) : (int64_t)4 << 30;
+        for (const DevSeg &ds : P.dsegs) n_max += std::min<int64_t>(ds.num_docs, (int64_t)ds.num_work * kTileDocs);
+        const int64_t sort_budget = env_i64("PHIP_DISTINCT_ROWS_SORT_BYTES", (int64_t)4 << 30);
         size_t tb = 0;
         if (n_max > INT32_MAX)
           return fail(PHIP_ERR_UNSUPPORTED, "SELECT DISTINCT: sorted keys over %lld docs, the limit is 2^31 - 1", (long long)n_max);
@@ -5352,75 +5451,56 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
           return fail(PHIP_ERR_UNSUPPORTED,
                       "SELECT DISTINCT: a key space of %lld rows needs sorted keys, whose buffers for %lld docs (%.0Lf bytes) "
                       "exceed PHIP_DISTINCT_ROWS_SORT_BYTES %lld",
-                      (long long)drq.key_space, (long long)n_max, need, (long long)sort_budget);
+                      (long long)P.drq.key_space, (long long)n_max, need, (long long)sort_budget);
       } else {
-        P.dr_bytes = (size_t)round_up(drq.num_words * 4, 16);
+        P.dr_bytes = (size_t)round_up(P.drq.num_words * 4, 16);
         rc = P.alloc(P.dr_bytes, &P.dr_bits);
         if (rc) return rc;
-        drq.bitmap = (uint32_t *)P.dr_bits;
-        P.dr_chunks = ceil_div(drq.num_words, kDistinctRowsChunkWords);
+        P.drq.bitmap = (uint32_t *)P.dr_bits;
+        P.dr_chunks = ceil_div(P.drq.num_words, kDistinctRowsChunkWords);
         void *cb;
         rc = P.alloc(((size_t)P.dr_chunks + 1) * 16, &cb);
         if (rc) return rc;
         P.dr_chunk_cnt = (int64_t *)cb;
         P.dr_chunk_off = P.dr_chunk_cnt + P.dr_chunks + 1;
-        P.dr_lds_bytes = drq.regime == DR_LDS ? (size_t)round_up(std::max<int64_t>(drq.num_words, 1) * 4, 16) : 0;
+        P.dr_lds_bytes = P.drq.regime == DR_LDS ? (size_t)round_up(std::max<int64_t>(P.drq.num_words, 1) * 4, 16) : 0;
       }
-      for (int k = 0; k < nsel; k++)
-        drd.values[k] = dr_values[k].empty() ? nullptr : (const uint64_t *)(base + dr_values_off[k]);
-      memcpy(blob.data.data() + dr_off, &drq, sizeof(drq));
-      P.sel_distinct = true;
-      P.dr_off = dr_off;
-      P.drq = drq;
-      P.dr_decode = drd;
+      for (int k = 0; k < P.nsel; k++)
+        P.dr_decode.values[k] = dr_values[k].empty() ? nullptr : (const uint64_t *)(P.base + dr_values_off[k]);
+      memcpy(blob.data.data() + P.dr_off, &P.drq, sizeof(P.drq));
       P.sel_keep = q->select_keep;
       // the LDS regime flushes once per workgroup: no more workgroups than stay resident; the others spread wider
-      P.dist_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * (drq.regime == DR_LDS ? 4 : 8));
+      P.dist_blocks = (int)std::min<int64_t>(4096, (int64_t)grid_cus * (P.drq.regime == DR_LDS ? 4 : 8));
     }
     P.select = true;
-    P.nsel = nsel;
-    P.sq_off = sq_off;
-    P.sel_types = sel_types;
-    P.sel_dicts = sel_dicts;
-    P.sel_str_ptrs.assign(nsel, {});
-    for (int k = 0; k < nsel; k++) {
+    P.sel_str_ptrs.assign(P.nsel, {});
+    for (int k = 0; k < P.nsel; k++) {
       if (sq.sel[k].kind != SEL_STR) continue;
       std::vector<const void *> &v = P.sel_str_ptrs[k];
-      v.resize(2 * (size_t)nseg);
-      for (int s = 0; s < nseg; s++) {
-        const ColumnStore &cs = segs[s]->cols[colidx[s][sq.sel[k].col_a]];
+      v.resize(2 * (size_t)P.nseg);
+      for (int s = 0; s < P.nseg; s++) {
+        const ColumnStore &cs = segp[s]->cols[colidx[s][sq.sel[k].col_a]];
         v[s] = cs.raw;
-        v[nseg + s] = cs.str_off;
+        v[P.nseg + s] = cs.str_off;
       }
     }
-    for (int k = 0; k < nsel; k++) {  // bytes one row reads per expression (first segment's widths)
+    for (int k = 0; k < P.nsel; k++) {  // bytes one row reads per expression (first segment's widths)
       for (int c : {sq.sel[k].col_a, sq.sel[k].expr != PHIP_EXPR_COLUMN ? sq.sel[k].col_b : -1}) {
         if (c < 0) continue;
-        const ColumnStore &cs = segs[0]->cols[colidx[0][c]];
+        const ColumnStore &cs = segp[0]->cols[colidx[0][c]];
         P.sel_bits.push_back(no_dict(cs) ? 0 : cs.bits);
         P.sel_width.push_back(cs.type == PHIP_TYPE_STRING ? 4 : type_width(cs.type));
       }
     }
   }
   // the descriptor blob goes up once, synchronously (its host copy dies with this function)
-  HIP_TRY(hipMemcpyAsync(dblob, blob.data.data(), blob.data.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(P.base, blob.data.data(), blob.data.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return PHIP_OK;
+}
 
-  P.dq = dq;
-  P.fq = fq;
-  P.dsegs = dsegs;
-  P.tasks = tasks;
-  P.gb_dicts = gb_dicts;
-  P.nseg = nseg;
-  P.nprog = nprog;
-  P.nmatch = nmatch;
-  P.naggs = naggs;
-  P.nhll = nhll;
-  P.log2m = log2m;
-  P.m_regs = m_regs;
-  P.num_group_by = q->num_group_by;
-  P.num_projected = num_projected;
-  P.prog_projected = prog_projected;
+// The server-level trim: its ORDER BY terms / keys / aggregation, and what a DISTINCTCOUNT beside it allows.
+int32_t PlanBuilder::finish_trim() {
   P.num_groups_limit = q->num_groups_limit;
   if (q->trim_size > 0 && q->num_order_terms > 0) {
     if (q->num_order_terms > kMaxOrderKeys || q->num_group_by > kMaxOrderKeys || !q->order_terms)
@@ -5452,8 +5532,8 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       ot.a[j] = t.a;
       ot.b[j] = t.b;
       if (t.kind == PHIP_ORDER_HLL) {  // (the function's register block and its own log2m)
-        ot.a[j] = dq.aggs[t.a].hll_slot;
-        ot.b[j] = dq.aggs[t.a].log2m;
+        ot.a[j] = P.dq.aggs[t.a].hll_slot;
+        ot.b[j] = P.dq.aggs[t.a].log2m;
       }
       ot.desc[j] = t.desc ? 1 : 0;
     }
@@ -5498,76 +5578,41 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
       return fail(PHIP_ERR_UNSUPPORTED, "ORDER BY a DISTINCTCOUNT / value counts over a key space of %lld above trim_size %lld",
                   (long long)gb_key_space, (long long)q->trim_size);
   }
-  P.total_work = total_work;
-  P.total_docs = total_docs;
+  return PHIP_OK;
+}
+
+// What an execution needs beyond the descriptors: the statistics' doc counts, the filter kernel's variant (decided
+// here, from the fusion flags: nothing before reads P.fused()), the id histogram's start, the timing events, the pinned
+// landing area, and how the plan completes -- the done ticket, the folded finalize, the record mode.
+int32_t PlanBuilder::finish_completion() {
   P.docs_in_work = 0;
-  for (const DevSeg &ds : dsegs) P.docs_in_work += ds.num_docs;
-  P.slot_docs.assign(nmatch, 0);
-  for (const DevSeg &ds : dsegs) P.slot_docs[ds.seg_index] = ds.num_docs;
-  P.has_filter = has_filter;
-  P.need_agg = need_agg;
-  P.need_mask = need_mask;
-  P.group_by = group_by;
+  for (const DevSeg &ds : P.dsegs) P.docs_in_work += ds.num_docs;
+  P.slot_docs.assign(P.nmatch, 0);
+  for (const DevSeg &ds : P.dsegs) P.slot_docs[ds.seg_index] = ds.num_docs;
   P.node_part = tl_node_docs > 0;
-  // (both fused shapes were decided for conjunctive programs only: conj_all, above)
+  // (both fused shapes were decided for conjunctive programs only: conj_all, configure_fusion)
   P.variant = fused_gb          ? (gb_lds ? FV_GB_LDS : gb_xcd ? FV_GB_XCD : FV_GB)
-              : fused_naggs > 0 ? (fused_lean ? FV_FUSED_LEAN : FV_FUSED)
-                                : (conj_only ? FV_CONJ : FV_GENERAL);
-  P.fused_naggs = fused_naggs;
-  P.want_bitmap = want_bitmap;
-  P.filter_nwords = filter_nwords;
-  P.filter_blocks = filter_blocks;
-  P.agg_blocks = agg_blocks;
-  P.filter_lds = filter_lds;
-  P.agg_lds = agg_lds;
+              : P.fused_naggs > 0 ? (fused_lean ? FV_FUSED_LEAN : FV_FUSED)
+                                : (conj_all ? FV_CONJ : FV_GENERAL);
   if (P.dq.hist_aggs) {
     // The id histogram pays for its per-segment flush and LDS only when most docs match (C4 SUM(M): 50 % 1.33 ->
     // 1.09 ms; 0.01-10 % slower, profiles/r06zt_hist_ab.log): the plan starts with the value gathers and takes the
     // histogram from the execution after one whose matched docs reached kHistMinMatch of its docs. The device
     // descriptor keeps hist_aggs; the host copy's decides which variant launches.
     P.hist_mask = P.dq.hist_aggs;
-    P.agg_lds_hist = agg_lds;
-    P.agg_lds_plain = agg_lds - (size_t)kAggWaves * P.dq.hist_words * 4;
+    P.agg_lds_hist = P.agg_lds;
+    P.agg_lds_plain = P.agg_lds - (size_t)kAggWaves * P.dq.hist_words * 4;
     P.dq.hist_aggs = 0;
     P.agg_lds = P.agg_lds_plain;
   }
-  P.base = base;
-  P.tasks_off = tasks_off;
-  P.rgroups_off = rgroups_off;
-  P.num_rgroups = rgroups.size();
-  P.mv_tasks_off = mv_tasks_off;
-  P.num_mv_tasks = mv_tasks.size();
-  P.mv_total_tiles = (int32_t)mv_total_tiles;
-  P.mv_max_blocks = std::max(1, grid_cus * 8);
-  P.mv_entries = mv_entries;
-  P.sm_tasks_off = sm_tasks_off;
-  P.num_sm_tasks = sm_tasks.size();
-  P.sm_total_tiles = (int32_t)sm_total_tiles;
-  P.sm_table_words = sm_table_words;
-  P.sm_entries = sm_entries;
-  P.dq_off = dq_off;
-  P.kinds_off = kinds_off;
-  P.inv_words = inv_words;
-  P.inv_words_total = inv_words_total;
-  P.fpart = fpart;
-  P.finals = finals;
-  P.seg_matched = seg_matched;
-  P.apart = apart;
-  P.masks = masks;
-  P.gtab = gtab;
-  P.ghll = ghll;
-  P.slab = slab;
-  P.hslab = hslab;
-  P.fo = fo;
-  P.first_doc = (uint32_t *)first_doc;
-  if (const char *te = getenv("PHIP_TOTAL_EVENTS")) P.total_events = atoi(te) != 0;
+  P.total_events = env_int("PHIP_TOTAL_EVENTS", 0) != 0;
   // ev[4] only between two launches (selection plans time their gather with it, execute_select)
   P.split_event = P.select || (P.has_filter && P.need_agg && !P.fused());
-  if (const char *se = getenv("PHIP_SPLIT_EVENT")) P.split_event = P.split_event || atoi(se) != 0;  // A/B
+  P.split_event = P.split_event || env_int("PHIP_SPLIT_EVENT", 0) != 0;  // A/B
   for (auto &e : P.ev) HIP_TRY(hipEventCreate(&e));
   {
     void *h = nullptr;
-    const size_t pbytes = (64 + (size_t)nmatch) * 8 + (size_t)std::max(nhll, 1) * (1 << 12) * 4;
+    const size_t pbytes = (64 + (size_t)P.nmatch) * 8 + (size_t)std::max(P.nhll, 1) * (1 << 12) * 4;
     // device-visible (mapped) pinned memory: finalize_all_kernel writes the results straight into it
     HIP_TRY(hipHostMalloc(&h, pbytes, hipHostMallocMapped));
     memset(h, 0, pbytes);
@@ -5576,7 +5621,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     HIP_TRY(hipHostGetDevicePointer(&dp, h, 0));
     P.pinned_dev = (uint64_t *)dp;
   }
-  if (!group_by && !P.select && !want_bitmap) {
+  if (!P.group_by && !P.select && !P.want_bitmap) {
     void *tk = nullptr;
     const int32_t trc = P.alloc(64, &tk);
     if (trc) return trc;
@@ -5590,25 +5635,25 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // profiles/r04w_host_ab.log; bench 0.284 -> 0.278 ms, profiles/r04x_bench.log), but every workgroup now waits for
   // its partials' acknowledgement and a ticket before it retires, and the fused kernel itself grows 11 % (sorted Q1.1
   // 0.135 -> 0.150 ms): its own roofline fraction drops more than the step gains. Opt-in (PHIP_FOLD_FINAL=1).
-  const char *ff = getenv("PHIP_FOLD_FINAL");
-  if (!group_by && !P.select && !want_bitmap && total_work > 0 && (has_filter || need_agg) && ff && atoi(ff) != 0 &&
-      P.ndist == 0) {
-    const bool fused = fused_naggs > 0;
-    const bool agg_last = need_agg && !fused;
-    const bool aggs_here = need_agg && naggs > 0;
+  int32_t rc = PHIP_OK;
+  if (!P.group_by && !P.select && !P.want_bitmap && P.total_work > 0 && (P.has_filter || P.need_agg) &&
+      env_int("PHIP_FOLD_FINAL", 0) != 0 && P.ndist == 0) {
+    const bool fused = P.fused_naggs > 0;
+    const bool agg_last = P.need_agg && !fused;
+    const bool aggs_here = P.need_agg && P.naggs > 0;
     DevFinal f;
     memset(&f, 0, sizeof(f));
-    f.pa = aggs_here ? (const uint64_t *)apart : nullptr;
-    f.ka = (const int32_t *)(base + kinds_off);
-    f.nba = fused ? filter_blocks : agg_blocks;
-    f.na = aggs_here ? naggs : 0;
-    f.pf = has_filter ? (const uint64_t *)fpart : nullptr;
-    f.kf = (const int32_t *)(base + kinds_off) + naggs;
-    f.nbf = filter_blocks;
-    f.segm = (uint64_t *)seg_matched;
-    f.nseg = nmatch;
-    f.hll = dq.hll_regs;
-    f.hll_words = nhll ? (int32_t)((size_t)nhll << log2m) : 0;
+    f.pa = aggs_here ? (const uint64_t *)P.apart : nullptr;
+    f.ka = (const int32_t *)(P.base + P.kinds_off);
+    f.nba = fused ? P.filter_blocks : P.agg_blocks;
+    f.na = aggs_here ? P.naggs : 0;
+    f.pf = P.has_filter ? (const uint64_t *)P.fpart : nullptr;
+    f.kf = (const int32_t *)(P.base + P.kinds_off) + P.naggs;
+    f.nbf = P.filter_blocks;
+    f.segm = (uint64_t *)P.seg_matched;
+    f.nseg = P.nmatch;
+    f.hll = P.dq.hll_regs;
+    f.hll_words = P.nhll ? (int32_t)((size_t)P.nhll << P.log2m) : 0;
     f.out = P.pinned_dev;
     void *fb;
     rc = P.alloc(round_up(sizeof(DevFinal), 64) + kFinCounterBytes, &fb);
@@ -5619,7 +5664,7 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
     P.fin_counter = f.counter;
     if (agg_last) {
       P.dq.fin = (const DevFinal *)fb;
-      HIP_TRY(hipMemcpyAsync(base + dq_off, &P.dq, sizeof(DevAggQuery), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(P.base + P.dq_off, &P.dq, sizeof(DevAggQuery), hipMemcpyHostToDevice, st));
     } else {
       P.fq.fin = (const DevFinal *)fb;
     }
@@ -5630,43 +5675,70 @@ static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t 
   // block's record within 128 B and every count within its 48-bit field. A plan that fails a condition keeps the
   // finalize launch.
   {
-    const char *hf = getenv("PHIP_HOST_FINAL");
-    const bool shape_ok = !group_by && !P.select && !want_bitmap && total_work > 0 && has_filter && nhll == 0 &&
-                          P.ndist == 0 && (fused_naggs > 0 ? P.fused_agg() && naggs <= 4 : !need_agg) &&
+    const bool shape_ok = !P.group_by && !P.select && !P.want_bitmap && P.total_work > 0 && P.has_filter && P.nhll == 0 &&
+                          P.ndist == 0 && (P.fused_naggs > 0 ? P.fused_agg() && P.naggs <= 4 : !P.need_agg) &&
                           (xcd_walk == 0 || xcd_walk == 2) && !P.fold_final && P.done_ticket != nullptr;
-    if (g_filter_records && shape_ok && !(hf && atoi(hf) == 0) && (double)P.total_docs * 64.0 < 281474976710656.0) {
-      std::vector<int32_t> entry_begin(dsegs.size());
-      P.rec_entry_slot.resize(dsegs.size());
-      for (size_t i = 0; i < dsegs.size(); i++) {
-        entry_begin[i] = dsegs[i].work_begin;
-        P.rec_entry_slot[i] = dsegs[i].seg_index;
+    if (g_filter_records && shape_ok && !env_off("PHIP_HOST_FINAL") && (double)P.total_docs * 64.0 < 281474976710656.0) {
+      std::vector<int32_t> entry_begin(P.dsegs.size());
+      P.rec_entry_slot.resize(P.dsegs.size());
+      for (size_t i = 0; i < P.dsegs.size(); i++) {
+        entry_begin[i] = P.dsegs[i].work_begin;
+        P.rec_entry_slot[i] = P.dsegs[i].seg_index;
       }
-      P.rec_na = fused_naggs > 0 ? naggs : 0;
-      P.rec_blocks = rec_block_table(xcd_walk, (int)total_work, filter_blocks, kFilterWaves, entry_begin);
+      P.rec_na = P.fused_naggs > 0 ? P.naggs : 0;
+      P.rec_blocks = rec_block_table(xcd_walk, (int)P.total_work, P.filter_blocks, kFilterWaves, entry_begin);
       if (rec_num_words(P.rec_na, P.rec_blocks.max_k) <= kRecMaxWords) {
         P.rec_stride = rec_num_words(P.rec_na, P.rec_blocks.max_k) <= 8 ? 64 : 128;
         P.rec_kinds.resize(std::max(P.rec_na, 1));
-        P.rec_scratch.resize(filter_blocks);
-        for (int a = 0; a < P.rec_na; a++) P.rec_kinds[a] = dq.aggs[a].acc;
+        P.rec_scratch.resize(P.filter_blocks);
+        for (int a = 0; a < P.rec_na; a++) P.rec_kinds[a] = P.dq.aggs[a].acc;
         void *h = nullptr, *dp = nullptr, *fd = nullptr;
-        const size_t rbytes = (size_t)filter_blocks * P.rec_stride;
+        const size_t rbytes = (size_t)P.filter_blocks * P.rec_stride;
         // coherent on purpose: the host reads the words while the kernel still runs
         HIP_TRY(hipHostMalloc(&h, rbytes, hipHostMallocMapped | hipHostMallocCoherent));
         memset(h, 0, rbytes);
         P.rec_area = (uint64_t *)h;
         HIP_TRY(hipHostGetDevicePointer(&dp, h, 0));
         P.rec_area_dev = (uint64_t *)dp;
-        rc = P.alloc((size_t)filter_blocks * 4, &fd);
+        rc = P.alloc((size_t)P.filter_blocks * 4, &fd);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(fd, P.rec_blocks.first.data(), (size_t)filter_blocks * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(fd, P.rec_blocks.first.data(), (size_t)P.filter_blocks * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
         P.rec_first_dev = (int32_t *)fd;
-        if (const char *t0 = getenv("PHIP_HOST_FINAL_TAG0")) P.rec_tag = (uint32_t)atoi(t0) & 0xffffu;  // (test hook)
+        P.rec_tag = (uint32_t)env_int("PHIP_HOST_FINAL_TAG0", 0) & 0xffffu;  // (test hook)
         P.rec_ok = true;
       }
     }
   }
   return PHIP_OK;
+}
+
+}  // namespace
+
+// Prepare a query: the phases of PlanBuilder in order, the first error ending the preparation (~Plan releases what the
+// phases allocated). The device's mutex is taken by resolve_inputs, once the segments name the device, and held by
+// the builder until this function returns.
+static int32_t prepare_plan(const phip_query_desc *q, bool want_bitmap, int64_t filter_nwords, Plan &P) {
+  P.want_bitmap = want_bitmap;
+  P.filter_nwords = filter_nwords;
+  PlanBuilder b(q, P);
+  int32_t rc;
+  if ((rc = b.resolve_inputs())) return rc;           // descriptor limits, segments, device (locked from here), columns
+  if ((rc = b.resolve_derived())) return rc;          // derived value columns: q rewritten to read them
+  if ((rc = b.resolve_group_keys())) return rc;       // multi-value misuse; tuple keys: q rewritten to one key column
+  if ((rc = b.plan_aggregations())) return rc;        // accumulators, projections, doc-order values, dense walk
+  if ((rc = b.plan_selection())) return rc;           // select expressions, ORDER BY terms, DISTINCT regime
+  if ((rc = b.plan_group_table())) return rc;         // projections counted, key space, dense / hash, distinct pass
+  if ((rc = b.stage_segments())) return rc;           // DevSegs, filter programs as postfix nodes, the work list
+  if ((rc = b.stage_inverted_leaves())) return rc;    // Roaring / MV scan / string-match tasks and their doc words
+  if ((rc = b.configure_filter_paths())) return rc;   // staged regions, conjunction paths, group-by records
+  if ((rc = b.configure_fusion())) return rc;         // fused aggregation / group-by / lean, small shape, byte counts
+  if ((rc = b.configure_filter_launch())) return rc;  // ring depth, walk, filter grid and LDS
+  if ((rc = b.configure_aggregation())) return rc;    // group table mode, GB_LDS walks, aggregation grid and LDS
+  if ((rc = b.allocate())) return rc;                 // the blob on the device, the filter descriptor, every buffer
+  if ((rc = b.finish_selection())) return rc;         // selection descriptors and scratch; the blob's upload
+  if ((rc = b.finish_trim())) return rc;              // the server-level trim
+  return b.finish_completion();                       // variant, events, landing area, ticket / fold / record mode
 }
 
 // Deadline / cancel checkpoint between an execution's launch phases (include/pinot_hip.h phip_plan_set_deadline).
@@ -7741,7 +7813,7 @@ int32_t phip::node_union_dictionary(const std::vector<uint64_t> &handles, const 
   std::vector<const ColumnStore *> cols;
   for (auto &sp : segs) {
     auto ci = sp->by_name.find(column);
-    if (ci == sp->by_name.end()) return PHIP_OK;  // (prepare_plan reports the missing column)
+    if (ci == sp->by_name.end()) return PHIP_OK;  // (resolve_inputs reports the missing column)
     const ColumnStore &c = sp->cols[ci->second];
     if (no_dict(c) || (type >= 0 && c.type != type)) return PHIP_OK;  // raw keys / mixed types: the record path
     type = c.type;

@@ -1,5 +1,5 @@
 // strmatch.hip -- REGEXP_LIKE / LIKE: a byte-level DFA walked over STRING values (device.h StrMatchTask; runtime.cpp
-// strmatch_image, the RAW_STRING_MATCH leaves of prepare_plan, phip_segment_match_dictionary; include/pinot_hip.h
+// strmatch_image, PlanBuilder::make_leaf / stage_inverted_leaves, phip_segment_match_dictionary; include/pinot_hip.h
 // "DFA blob").
 //
 // The reference runs java.util.regex's Matcher.reset(value).find() per scanned doc (RegexpLikePredicateEvaluator-

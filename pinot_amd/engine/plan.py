@@ -1606,7 +1606,7 @@ DISTINCT_ROWS_MAX_BYTES = 256 << 20        # default PHIP_DISTINCT_ROWS_MAX_BYTE
 
 
 def distinct_rows_plan(cards, order_terms, lds_words=None, max_bytes=None):
-    """The key layout and the regime of a SELECT DISTINCT on the device (runtime.cpp prepare_plan's arithmetic, as a
+    """The key layout and the regime of a SELECT DISTINCT on the device (runtime.cpp plan_selection's arithmetic, as a
     pure function). ``cards``: the query-global cardinality of every DISTINCT column in select order; ``order_terms``:
     [(select index, descending)] of the ORDER BY. ``lds_words`` / ``max_bytes``: PHIP_DISTINCT_LDS_WORDS /
     PHIP_DISTINCT_ROWS_MAX_BYTES (None: the environment's value, else the default).
