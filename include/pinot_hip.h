@@ -331,6 +331,62 @@ typedef struct phip_aggregation {
   int32_t program; /* filter program whose docs this aggregation reads (0 unless num_filter_programs > 1) */
 } phip_aggregation;
 
+/* A time transform of one single-value dictionary INT / LONG column (dateTrunc, toEpochSeconds ... toEpochDays,
+ * timeConvert, and the UTC ISO-chronology fields; DateTruncTransformFunction.java:100-142, DateTimeFunctions.java:80-133
+ * and :656-1034, TimeConversionTransformFunction.java). The value of a dictionary entry v is
+ *     scale(op(scale(v, in_mul, in_div)), out_mul, out_div)
+ * where scale(x, m, d) is x * m or Java's x / d (truncating toward zero; of m and d one is 1, both >= 1) and op works
+ * on UTC epoch milliseconds: PHIP_TT_CONVERT the identity (unit 0, no output scale), PHIP_TT_TRUNC Joda's roundFloor
+ * to `unit` = PHIP_TT_SECOND ... PHIP_TT_YEAR (floors below 1970 too; ISO weeks from Monday; the proleptic Gregorian
+ * calendar), PHIP_TT_FIELD the field `unit` = PHIP_TT_FIELD_YEAR ... PHIP_TT_FIELD_MILLISECOND (no scales; dayOfWeek
+ * 1 = Monday ... 7 = Sunday, week = the ISO week of the weekyear). TimeUnit.convert's saturation is not reproduced: a
+ * program whose products over the column's [min, max] could leave int64 is PHIP_ERR_UNSUPPORTED. function 0
+ * (PHIP_TT_NONE) = the plain column. Any other malformed program is PHIP_ERR_INVALID, before any launch. */
+#define PHIP_TT_NONE 0
+#define PHIP_TT_CONVERT 1
+#define PHIP_TT_TRUNC 2
+#define PHIP_TT_FIELD 3
+#define PHIP_TT_SECOND 0
+#define PHIP_TT_MINUTE 1
+#define PHIP_TT_HOUR 2
+#define PHIP_TT_DAY 3
+#define PHIP_TT_WEEK 4
+#define PHIP_TT_MONTH 5
+#define PHIP_TT_QUARTER 6
+#define PHIP_TT_YEAR 7
+#define PHIP_TT_FIELD_YEAR 0
+#define PHIP_TT_FIELD_QUARTER 1
+#define PHIP_TT_FIELD_MONTH 2
+#define PHIP_TT_FIELD_WEEK 3
+#define PHIP_TT_FIELD_DAY_OF_YEAR 4
+#define PHIP_TT_FIELD_DAY_OF_MONTH 5
+#define PHIP_TT_FIELD_DAY_OF_WEEK 6
+#define PHIP_TT_FIELD_HOUR 7
+#define PHIP_TT_FIELD_MINUTE 8
+#define PHIP_TT_FIELD_SECOND 9
+#define PHIP_TT_FIELD_MILLISECOND 10
+typedef struct phip_time_transform {
+  int32_t function; /* PHIP_TT_* */
+  int32_t unit;
+  int64_t in_mul, in_div, out_mul, out_div;
+} phip_time_transform;
+
+/* A comparison of a time transform's values with int64 literals (phip_segment_match_transform): PHIP_TT_PRED_RANGE =
+ * lower <= / < value <= / < upper by the inclusive flags (an unbounded side: INT64_MIN / INT64_MAX inclusive);
+ * PHIP_TT_PRED_SET = value among the num_values strictly ascending `values` (0 values: nothing). exclusive = 1
+ * complements the answer (NOT_EQ / NOT_IN). */
+#define PHIP_TT_PRED_RANGE 1
+#define PHIP_TT_PRED_SET 2
+typedef struct phip_transform_predicate {
+  int32_t kind;
+  int32_t exclusive;
+  int64_t lower, upper;
+  int32_t lower_inclusive, upper_inclusive;
+  const int64_t *values;
+  int32_t num_values;
+  int32_t reserved;
+} phip_transform_predicate;
+
 typedef struct phip_query_desc {
   int32_t num_columns;
   int32_t num_segments;
@@ -434,6 +490,18 @@ typedef struct phip_query_desc {
    * devices (a node plan), a library built without the distinct-rows kernels. All zero = not a distinct query. */
   int32_t select_distinct;
   int32_t reserved_select_distinct;
+  /* GROUP BY over time transforms: null, or num_group_by programs, one per group-by column; function PHIP_TT_NONE = the
+   * plain column. Key k is then program k's value of group_by_columns[k] (which stays the real column's index: a
+   * single-value dictionary INT / LONG column in every segment): the group-by walks gather the same per-segment id
+   * remap as for a plain key, only its query-global ids number the ascending distinct values of the program over the
+   * segments' dictionaries (built on the device once per (segments, column, program) and kept with the other remaps),
+   * so id order is value order and the table choice, tuple keys, key-ordered trims, num_groups_limit and
+   * phip_result_dictionary (data type LONG, or INT for a PHIP_TT_FIELD) work as for any key. Two keys over one column
+   * must name it through two entries of columns[] (each entry carries one remap). A transformed key's plan builds no
+   * group-by records. PHIP_ERR_INVALID: a malformed program, a column that is not such a column. PHIP_ERR_UNSUPPORTED:
+   * a node plan (segments on several devices), null_group_by on a transformed key whose column has a null vector, a
+   * program that could overflow, a library built without the kernel. */
+  const struct phip_time_transform *group_by_transforms;
 } phip_query_desc;
 
 typedef struct phip_select_order_term {
@@ -573,6 +641,20 @@ PHIP_API int32_t phip_segment_device_bytes(uint64_t handle, uint64_t *out_bytes)
  * the kernel. */
 PHIP_API int32_t phip_segment_match_dictionary(uint64_t handle, const char *column, const int32_t *dfa, int32_t dfa_words,
                                                uint64_t *out_words, int64_t num_words);
+/* The twin of phip_segment_match_dictionary for a time transform over a single-value dictionary INT /
+ * LONG column: evaluates `transform` once per dictionary entry and compares it with `predicate`. Bit i % 64 of
+ * out_words[i / 64] is set iff entry i's value passes; bits at and past the cardinality are 0. The caller turns the
+ * ids into DICT_RANGE / DICT_SET leaves flagged PHIP_LEAF_FLAG_ALWAYS_SCAN (ExpressionFilterOperator always scans).
+ * Every field is validated before any launch: PHIP_ERR_INVALID for a malformed program or predicate (an unknown kind,
+ * values that do not ascend strictly, a null `values` with num_values > 0), a column that is not a dictionary INT /
+ * LONG column, too few words; PHIP_ERR_UNSUPPORTED for a program that could overflow over the column's values and in
+ * a library built without the kernel. */
+PHIP_API int32_t phip_segment_match_transform(uint64_t handle, const char *column, const phip_time_transform *transform,
+                                              const phip_transform_predicate *predicate, uint64_t *out_words,
+                                              int64_t num_words);
+/* Since phip_init: the transformed group-by remaps built (a plan that finds its remap kept builds none) and the
+ * phip_segment_match_transform launches. */
+PHIP_API int32_t phip_transform_info(int64_t *out_remap_builds, int64_t *out_match_launches);
 /* The segment's derived value columns (phip_query_desc.derived): how many it holds now (at most 16), their bytes, and
  * the materialise launches since load -- a plan whose expression the segment already holds launches none.
  * phip_segment_device_bytes stays what the segment's load pinned: it does not include these bytes (nor the other

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "phip_runtime_versions", "phip_plan_abandon_partial", "phip_result_select_dictionary",
     "phip_plan_set_deadline", "phip_plan_cancel", "phip_plan_exchange", "phip_result_distinct_dictionary",
     "phip_plan_launch_shape", "phip_segment_derived_info", "phip_segment_match_dictionary",
+    "phip_segment_match_transform", "phip_transform_info",
 )
 
 # phip_plan_exchange kinds (include/pinot_hip.h "node plans")
@@ -128,6 +129,22 @@ class DerivedColumn(ctypes.Structure):
     _fields_ = [("ops", ctypes.POINTER(ExprOp)), ("num_ops", ctypes.c_int32), ("reduction", ctypes.c_int32)]
 
 
+class TimeTransform(ctypes.Structure):
+    """phip_time_transform: a time transform's canonical program (query/time_transform.py Program)."""
+    _fields_ = [("function", ctypes.c_int32), ("unit", ctypes.c_int32), ("in_mul", ctypes.c_int64),
+                ("in_div", ctypes.c_int64), ("out_mul", ctypes.c_int64), ("out_div", ctypes.c_int64)]
+
+
+TT_PRED_RANGE, TT_PRED_SET = 1, 2
+
+
+class TransformPredicate(ctypes.Structure):
+    """phip_transform_predicate: a comparison of a time transform's values with int64 literals."""
+    _fields_ = [("kind", ctypes.c_int32), ("exclusive", ctypes.c_int32), ("lower", ctypes.c_int64),
+                ("upper", ctypes.c_int64), ("lower_inclusive", ctypes.c_int32), ("upper_inclusive", ctypes.c_int32),
+                ("values", ctypes.POINTER(ctypes.c_int64)), ("num_values", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class QueryDesc(ctypes.Structure):
     _fields_ = [("num_columns", ctypes.c_int32), ("num_segments", ctypes.c_int32),
                 ("columns", ctypes.POINTER(ctypes.c_char_p)), ("segments", ctypes.POINTER(ctypes.c_uint64)),
@@ -146,7 +163,8 @@ class QueryDesc(ctypes.Structure):
                 ("derived", ctypes.POINTER(DerivedColumn)),
                 ("num_select_order", ctypes.c_int32), ("reserved_select_order", ctypes.c_int32),
                 ("select_order", ctypes.POINTER(SelectOrderTerm)), ("select_keep", ctypes.c_int64),
-                ("select_distinct", ctypes.c_int32), ("reserved_select_distinct", ctypes.c_int32)]
+                ("select_distinct", ctypes.c_int32), ("reserved_select_distinct", ctypes.c_int32),
+                ("group_by_transforms", ctypes.POINTER(TimeTransform))]
 
 
 class Result(ctypes.Structure):
@@ -272,6 +290,13 @@ def load(with_torch: bool = False):
     lib.phip_segment_derived_info.restype = i32
     lib.phip_segment_match_dictionary.argtypes = [u64, ctypes.c_char_p, ctypes.POINTER(i32), i32, ctypes.POINTER(u64), i64]
     lib.phip_segment_match_dictionary.restype = i32
+    mt = getattr(lib, "phip_segment_match_transform", None)  # (absent from an older library loaded for an A/B run)
+    if mt is not None:
+        mt.argtypes = [u64, ctypes.c_char_p, ctypes.POINTER(TimeTransform), ctypes.POINTER(TransformPredicate),
+                       ctypes.POINTER(u64), i64]
+        mt.restype = i32
+        lib.phip_transform_info.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        lib.phip_transform_info.restype = i32
     lib.phip_query.argtypes = [ctypes.POINTER(QueryDesc), ctypes.POINTER(ctypes.POINTER(Result))]
     lib.phip_query.restype = i32
     lib.phip_result_dictionary.argtypes = [ctypes.POINTER(Result), i32, ctypes.POINTER(DictionaryView)]

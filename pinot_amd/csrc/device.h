@@ -238,6 +238,31 @@ struct StrMatchTask {
   int32_t invert;
 };
 
+// A time transform over one numeric dictionary (transform.hip dict_transform_kernel; civil.h time_transform; include/
+// pinot_hip.h phip_time_transform): entry i of the `card` LE INT / LONG values at `dict`. `values` (or null) takes the
+// results' order-preserving u64 images (value ^ 2^63: unsigned order = signed order). `match` (or null) takes the
+// predicate's dense id words -- bit i % 64 of u64 word i / 64, tile t's 32 words at match + t * 32, every word of tiles
+// [0, ceil(card / 2048)) written, zeros past card, as strmatch_kernel leaves its words. The predicate: a range over
+// [lo, hi] with the inclusive flags, or membership in the `set_count` ascending values at `set`; `invert` complements
+// it within card.
+constexpr int kTtPredRange = 1, kTtPredSet = 2;
+struct TransformTask {
+  const void *dict;
+  uint64_t *values;
+  uint64_t *match;
+  const int64_t *set;
+  int64_t in_mul, in_div, out_mul, out_div;
+  int64_t lo, hi;
+  int32_t function, unit;
+  int32_t type;  // PHIP_TYPE_INT / PHIP_TYPE_LONG
+  int32_t card;
+  int32_t pred;  // kTtPredRange / kTtPredSet (with match)
+  int32_t lo_inclusive, hi_inclusive;
+  int32_t set_count;
+  int32_t invert;
+  int32_t pad;
+};
+
 // One group-by column's key id source for the tuple packing of key spaces above 2^62 (keys.hip tuple_words_kernel).
 constexpr int kMaxTupleCols = 8;
 constexpr int kMaxTupleWords = 4;

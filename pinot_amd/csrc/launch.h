@@ -199,6 +199,16 @@ struct DistinctRowsLaunchers {
 };
 void register_distinct_rows_launchers(const DistinctRowsLaunchers *l);  // defined in runtime.cpp
 
+// ---- transform.hip (time transforms over a dictionary) ------------------------------------------------------------
+// Registered like ExprLauncher (null in the host simulation: a transformed group-by key or phip_segment_match_transform
+// is then PHIP_ERR_UNSUPPORTED). dict: the task in device memory, its ceil(card / 2048) tiles on at most max_blocks
+// workgroups. remap: out[i] = the position of images[i] among the u ascending distinct images at uniq, i < n.
+struct TransformLaunchers {
+  hipError_t (*dict)(const TransformTask *task, int32_t card, int max_blocks, hipStream_t s);
+  hipError_t (*remap)(const uint64_t *images, int64_t n, const uint64_t *uniq, int64_t u, int32_t *out, hipStream_t s);
+};
+void register_transform_launchers(const TransformLaunchers *l);  // defined in runtime.cpp
+
 // ---- keys.hip ----------------------------------------------------------------------------------------------------
 hipError_t set_str_hash_bits(int bits);
 hipError_t launch_raw_images(const void *raw, int32_t type, int64_t n, uint64_t *out, hipStream_t s);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/pinot_hip.h"
+#include "civil.h"
 #include "device.h"
 #include "fused_shape.h"
 #include "host_final.h"
@@ -346,6 +347,9 @@ static phip::ExprLauncher g_expr_launcher = nullptr;
 static const phip::MvLaunchers *g_mv = nullptr;
 // strmatch.hip's launcher (launch.h StrMatchLaunchers): null in a library without the kernel unit
 static const phip::StrMatchLaunchers *g_strmatch = nullptr;
+// transform.hip's launchers (launch.h TransformLaunchers): null in a library without the kernel unit
+static const phip::TransformLaunchers *g_transform = nullptr;
+static std::atomic<int64_t> g_transform_remap_builds{0}, g_transform_match_launches{0};  // phip_transform_info
 // select_order.hip's launchers (launch.h SelectOrderLaunchers): null in a library without the kernel unit
 static const phip::SelectOrderLaunchers *g_sel_order = nullptr;
 // distinct_rows.hip's launchers (launch.h DistinctRowsLaunchers): null in a library without the kernel unit
@@ -1334,6 +1338,156 @@ static int32_t raw_real_key_ids(Device &dev, const std::vector<Segment *> &segs,
   return PHIP_OK;
 }
 
+// ---- time transforms over a dictionary (include/pinot_hip.h phip_time_transform; civil.h; transform.hip) ----------
+static int32_t time_program(const phip_time_transform *t, TimeProgram *out) {
+  if (!t) return fail(PHIP_ERR_INVALID, "time transform: null program");
+  TimeProgram p{t->function, t->unit, t->in_mul, t->in_div, t->out_mul, t->out_div};
+  if (!time_program_valid(p))
+    return fail(PHIP_ERR_INVALID, "time transform: malformed program (function %d, unit %d, scales %lld / %lld, %lld / %lld)",
+                p.function, p.unit, (long long)p.in_mul, (long long)p.in_div, (long long)p.out_mul, (long long)p.out_div);
+  *out = p;
+  return PHIP_OK;
+}
+static std::string time_program_key(const TimeProgram &p) {
+  return "#tt" + std::to_string(p.function) + "." + std::to_string(p.unit) + "." + std::to_string(p.in_mul) + "." +
+         std::to_string(p.in_div) + "." + std::to_string(p.out_mul) + "." + std::to_string(p.out_div);
+}
+// What a time transform reads: a single-value dictionary INT / LONG column whose values the program cannot overflow on.
+static int32_t time_transform_column(const ColumnStore &c, const TimeProgram &p) {
+  if ((c.type != PHIP_TYPE_INT && c.type != PHIP_TYPE_LONG) || no_dict(c) || is_mv(c) || c.dict == nullptr ||
+      c.host_dict.size() != (size_t)c.card * (size_t)type_width(c.type))
+    return fail(PHIP_ERR_INVALID, "time transform: column %s is not a single-value dictionary INT / LONG column", c.name.c_str());
+  if (c.card > 0 && (!c.has_range || !time_transform_fits(p, c.vmin, c.vmax)))
+    return fail(PHIP_ERR_UNSUPPORTED, "time transform over column %s: its values [%lld, %lld] could leave the LONG range",
+                c.name.c_str(), (long long)c.vmin, (long long)c.vmax);
+  return PHIP_OK;
+}
+static void fill_transform_task(TransformTask &t, const ColumnStore &c, const TimeProgram &p) {
+  memset(&t, 0, sizeof(t));
+  t.dict = c.dict;
+  t.type = c.type;
+  t.card = c.card;
+  t.function = p.function;
+  t.unit = p.unit;
+  t.in_mul = p.in_mul;
+  t.in_div = p.in_div;
+  t.out_mul = p.out_mul;
+  t.out_div = p.out_div;
+}
+static int transform_grid_blocks(const Device &dev) {
+  int grid_cus = dev.num_cus;
+  if (const char *gc = getenv("PHIP_GRID_CUS"))
+    if (atoi(gc) >= 1) grid_cus = atoi(gc);
+  return std::max(1, grid_cus * 8);
+}
+
+// GROUP BY f(col) over a dictionary column: the group-by walks gather remap[local id] as for any key; here the
+// query-global ids number the ascending distinct values of f over the segments' dictionaries. Per segment
+// dict_transform_kernel writes the entries' order-preserving images, launch_sort_unique_u64 makes them distinct -- per
+// segment and then over the segments' distinct images, as raw_real_key_ids does -- and transform_remap_kernel finds
+// each entry's position. Built on the device's setup stream once per (column, program, segments), cached with the
+// other remaps. Never the identity map; the result's dictionary holds the transformed values (LONG, or INT for a field).
+static int32_t transformed_key_remap(Device &dev, const std::vector<Segment *> &segs, const std::vector<int> &colidx,
+                                     const std::string &name, const TimeProgram &prog, Device::Remap &r) {
+  if (!g_transform)
+    return fail(PHIP_ERR_UNSUPPORTED, "a time transform of group-by column %s: this library was built without the "
+                "transform kernels", name.c_str());
+  hipStream_t st = dev.stream;
+  std::vector<void *> tmp;  // freed on every return
+  struct Free {
+    std::vector<void *> &v;
+    ~Free() {
+      for (void *p : v) (void)hipFree(p);
+    }
+  } free_tmp{tmp};
+  auto alloc = [&](size_t bytes, void **p) -> int32_t {
+    HIP_TRY(hipMalloc(p, std::max<size_t>(bytes, 16)));
+    tmp.push_back(*p);
+    return PHIP_OK;
+  };
+  const size_t S = segs.size();
+  for (size_t i = 0; i < S; i++) {
+    int32_t rc = time_transform_column(segs[i]->cols[colidx[i]], prog);
+    if (rc) return rc;
+  }
+  const int max_blocks = transform_grid_blocks(dev);
+  std::vector<uint64_t *> seg_img(S, nullptr), seg_uniq(S, nullptr);
+  std::vector<int64_t> seg_u(S, 0);
+  std::vector<TransformTask> tasks(S);  // (the staging of the tasks' copies: alive until the last synchronize)
+  int64_t total = 0;
+  int32_t rc;
+  for (size_t i = 0; i < S; i++) {
+    const ColumnStore &c = segs[i]->cols[colidx[i]];
+    const int64_t n = c.card;
+    if (n <= 0) continue;
+    void *task, *img, *srt, *uq, *cnt, *scratch;
+    size_t sb = 0;
+    if ((rc = alloc(sizeof(TransformTask), &task)) || (rc = alloc((size_t)n * 8, &img)) || (rc = alloc((size_t)n * 8, &srt)) ||
+        (rc = alloc((size_t)n * 8, &uq)) || (rc = alloc(8, &cnt)))
+      return rc;
+    HIP_TRY(launch_sort_unique_u64(nullptr, &sb, nullptr, nullptr, nullptr, nullptr, n, st));
+    if ((rc = alloc(sb, &scratch))) return rc;
+    fill_transform_task(tasks[i], c, prog);
+    tasks[i].values = (uint64_t *)img;
+    HIP_TRY(hipMemcpyAsync(task, &tasks[i], sizeof(TransformTask), hipMemcpyHostToDevice, st));
+    HIP_TRY(g_transform->dict((const TransformTask *)task, c.card, max_blocks, st));
+    HIP_TRY(launch_sort_unique_u64(scratch, &sb, (uint64_t *)img, (uint64_t *)srt, (uint64_t *)uq, (int64_t *)cnt, n, st));
+    HIP_TRY(hipMemcpyAsync(&seg_u[i], cnt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (seg_u[i] < 0 || seg_u[i] > n) return fail(PHIP_ERR_HIP, "time transform of column %s: %lld distinct values of %lld", name.c_str(), (long long)seg_u[i], (long long)n);
+    seg_img[i] = (uint64_t *)img;
+    seg_uniq[i] = (uint64_t *)uq;
+    total += seg_u[i];
+  }
+  void *all, *srt, *guniq, *cnt, *scratch;
+  size_t sb = 0;
+  if ((rc = alloc((size_t)total * 8, &all)) || (rc = alloc((size_t)total * 8, &srt)) ||
+      (rc = alloc((size_t)total * 8, &guniq)) || (rc = alloc(8, &cnt)))
+    return rc;
+  int64_t off = 0;
+  for (size_t i = 0; i < S; i++) {
+    if (!seg_u[i]) continue;
+    HIP_TRY(hipMemcpyAsync((uint64_t *)all + off, seg_uniq[i], (size_t)seg_u[i] * 8, hipMemcpyDeviceToDevice, st));
+    off += seg_u[i];
+  }
+  HIP_TRY(launch_sort_unique_u64(nullptr, &sb, nullptr, nullptr, nullptr, nullptr, total, st));
+  if ((rc = alloc(sb, &scratch))) return rc;
+  int64_t u = 0;
+  HIP_TRY(launch_sort_unique_u64(scratch, &sb, (uint64_t *)all, (uint64_t *)srt, (uint64_t *)guniq, (int64_t *)cnt, total, st));
+  HIP_TRY(hipMemcpyAsync(&u, cnt, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (u < 0 || u > total) return fail(PHIP_ERR_HIP, "time transform of column %s: %lld distinct values of %lld", name.c_str(), (long long)u, (long long)total);
+  if (u > INT32_MAX) return fail(PHIP_ERR_UNSUPPORTED, "time transform of column %s: %lld distinct values", name.c_str(), (long long)u);
+  r.dev.assign(S, nullptr);
+  for (size_t i = 0; i < S; i++) {
+    const int64_t n = segs[i]->cols[colidx[i]].card;
+    void *p;
+    HIP_TRY(hipMalloc(&p, std::max<size_t>((size_t)std::max<int64_t>(n, 0) * 4, 16)));
+    r.dev[i] = (int32_t *)p;  // owned by r from here
+    if (n > 0) HIP_TRY(g_transform->remap(seg_img[i], n, (const uint64_t *)guniq, u, (int32_t *)p, st));
+  }
+  std::vector<uint64_t> img((size_t)u);
+  if (u) HIP_TRY(hipMemcpyAsync(img.data(), guniq, (size_t)u * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const bool field = prog.function == kTtField;
+  const int w = field ? 4 : 8;
+  r.values.assign((size_t)u * w, 0);
+  for (int64_t i = 0; i < u; i++) {  // the images back to values
+    const int64_t v = (int64_t)(img[(size_t)i] ^ 0x8000000000000000ull);
+    if (field) {
+      const int32_t v32 = (int32_t)v;
+      memcpy(r.values.data() + 4 * i, &v32, 4);
+    } else {
+      memcpy(r.values.data() + 8 * i, &v, 8);
+    }
+  }
+  r.type = field ? PHIP_TYPE_INT : PHIP_TYPE_LONG;
+  r.width = 0;
+  r.card = (int32_t)u;
+  g_transform_remap_builds++;
+  return PHIP_OK;
+}
+
 // Raw STRING keys (the no-dictionary generators key a String by its value): per segment the docs' 64-bit hashes are
 // sorted and made unique on the device with a representative doc each, every doc is compared with its representative
 // (keys.hip), the representatives' bytes come to the host, which checks equal hashes across segments hold equal
@@ -1699,7 +1853,32 @@ static thread_local const NodeDicts *tl_node_dicts = nullptr;
 static thread_local int64_t tl_node_docs = 0;
 
 int32_t build_remap(Device &dev, const std::vector<Segment *> &segs, const std::vector<int> &colidx,
-                    const std::string &name, std::shared_ptr<Device::Remap> &out, bool skip_nulls = false) {
+                    const std::string &name, std::shared_ptr<Device::Remap> &out, bool skip_nulls = false,
+                    const phip_time_transform *tt = nullptr) {
+  if (tt && tt->function != PHIP_TT_NONE) {
+    // a transformed key (transformed_key_remap): the column's node-global dictionary does not apply to it
+    TimeProgram prog;
+    int32_t rc = time_program(tt, &prog);
+    if (rc) return rc;
+    if (tl_node_dicts != nullptr)
+      return fail(PHIP_ERR_UNSUPPORTED, "a time transform of group-by column %s in a node plan", name.c_str());
+    if (skip_nulls)
+      return fail(PHIP_ERR_UNSUPPORTED, "a time transform of group-by column %s, which has a null vector, under null "
+                  "handling", name.c_str());
+    std::string key = name + time_program_key(prog);
+    for (auto *s : segs) key += ":" + std::to_string(s->handle);
+    auto it = dev.remaps.find(key);
+    if (it != dev.remaps.end()) {
+      out = it->second;
+      return PHIP_OK;
+    }
+    auto r = std::make_shared<Device::Remap>();
+    rc = transformed_key_remap(dev, segs, colidx, name, prog, *r);
+    if (rc) return rc;
+    dev.remaps[key] = r;
+    out = r;
+    return PHIP_OK;
+  }
   auto git = dev.globals.find(name);
   const Device::GlobalDict *gd = git == dev.globals.end() ? nullptr : &git->second;
   // a node plan's part (node_plan_create): the column keyed by the node plan's own union dictionary
@@ -2472,6 +2651,7 @@ static int32_t build_records(Segment &sg, const phip_query_desc *q, DevAggQuery 
 void phip::register_expr_launcher(ExprLauncher f) { g_expr_launcher = f; }
 void phip::register_mv_launchers(const MvLaunchers *l) { g_mv = l; }
 void phip::register_strmatch_launchers(const StrMatchLaunchers *l) { g_strmatch = l; }
+void phip::register_transform_launchers(const TransformLaunchers *l) { g_transform = l; }
 void phip::register_select_order_launchers(const SelectOrderLaunchers *l) { g_sel_order = l; }
 void phip::register_distinct_rows_launchers(const DistinctRowsLaunchers *l) { g_distinct_rows = l; }
 // the filter kernels of this library store records (filter.hip registers it; false in a build without the kernel units,
@@ -2836,6 +3016,10 @@ struct PlanBuilder {
     const ColumnStore &cs = segp[s]->cols[colidx[s][c]];
     return no_dict(cs) || (use_vals[c] && (packed_vals(cs) || cs.vals != nullptr) && vals_eligible(cs, vals_min));
   }
+  // group-by key k's time transform (phip_query_desc.group_by_transforms), or null: the plain column
+  const phip_time_transform *key_transform(int k) const {
+    return q->group_by_transforms && q->group_by_transforms[k].function != PHIP_TT_NONE ? &q->group_by_transforms[k] : nullptr;
+  }
   bool fused_any() const { return P.fused_naggs > 0 || fused_gb; }  // the filter kernel aggregates its own tiles
   int entry_slot() const {  // the next inverted leaf's index among those of the entry being lowered
     int slot = 0;
@@ -2898,6 +3082,7 @@ struct PlanBuilder {
   bool hll_made = false, hll_doc_on = false;
   std::vector<bool> hll_doc_used, hll_doc16_used;  // (segment, column): HLL entries read by doc / 16-bit ones
   bool rec_want = false;
+  bool gb_transformed = false;  // some group-by key is a time transform of its column (no group-by records then)
   int rec_min_fields = kRecMinFields;
   size_t segs_off = 0, nodes_off = 0;
   std::vector<int32_t> node_inv_slot, node_inv_leaves;  // per node: an inverted leaf's slot / its entry's leaves
@@ -3126,6 +3311,30 @@ int32_t PlanBuilder::resolve_group_keys() {
     }
   }
 
+  // Time transforms of group-by keys (phip_query_desc.group_by_transforms): every program checked before anything is
+  // built. A transformed key owns its entry of columns[]: the entry's DevCol carries one remap.
+  for (int k = 0; k < q->num_group_by && q->group_by_columns && q->group_by_transforms; k++) {
+    if (q->group_by_transforms[k].function == PHIP_TT_NONE) continue;
+    TimeProgram prog;
+    int32_t rc = time_program(&q->group_by_transforms[k], &prog);
+    if (rc) return rc;
+    const int c = q->group_by_columns[k];
+    if (c < 0 || c >= nreal) return fail(PHIP_ERR_INVALID, "group_by_columns[%d] = %d: a time transform reads a column of the query", k, c);
+    for (int j = 0; j < q->num_group_by; j++)
+      if (j != k && q->group_by_columns[j] == c)
+        return fail(PHIP_ERR_INVALID, "group-by keys %d and %d share entry %d of columns[]: a transformed key needs its own", j, k, c);
+    for (int a = 0; a < P.naggs && q->aggregations; a++)
+      if ((q->aggregations[a].function == PHIP_AGG_DISTINCT || q->aggregations[a].function == PHIP_AGG_VALUE_COUNTS) &&
+          q->aggregations[a].column_a == c)
+        return fail(PHIP_ERR_INVALID, "aggregation %d and the transformed group-by key %d share entry %d of columns[]", a, k, c);
+    if (!g_transform)
+      return fail(PHIP_ERR_UNSUPPORTED, "a time transform of group-by column %s: this library was built without the "
+                  "transform kernels", q->columns[c]);
+    for (int s = 0; s < P.nseg; s++)
+      if ((rc = time_transform_column(segp[s]->cols[colidx[s][c]], prog))) return rc;
+    gb_transformed = true;
+  }
+
   // A group-by whose mixed-radix key space exceeds 2^62 groups by tuple keys (build_tuple_keys): the plan is made for
   // one virtual key column (the first group-by column's slot carries its ids) and execute_plan expands the keys.
   // Device trims that order by a group key need the columns' order, so such a plan returns every group instead.
@@ -3142,7 +3351,7 @@ int32_t PlanBuilder::resolve_group_keys() {
       if ((q->null_group_by >> k) & 1)
         for (int s = 0; s < P.nseg; s++) null_key |= segp[s]->cols[ci[s]].nulls != nullptr;
       std::shared_ptr<Device::Remap> r;
-      int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], r, null_key);
+      int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], r, null_key, key_transform(k));
       if (rc) return rc;
       dicts.push_back(r);
       radix.push_back((int64_t)r->card + (null_key ? 1 : 0));
@@ -3161,6 +3370,7 @@ int32_t PlanBuilder::resolve_group_keys() {
       qv = *q;
       qv.num_group_by = 1;
       qv.group_by_columns = P.tuple_gb_col;
+      qv.group_by_transforms = nullptr;  // (the tuple remap holds the transformed ids)
       qv.null_group_by = 0;
       bool key_terms = qv.num_order_by_keys > 0;
       for (int j = 0; j < qv.num_order_terms && qv.order_terms; j++) key_terms |= qv.order_terms[j].kind == PHIP_ORDER_GROUP_KEY;
@@ -3761,6 +3971,13 @@ int32_t PlanBuilder::plan_selection() {
 // The projections the statistics count, the group-by key space and its table's placement (dense / hash), and the
 // descriptor of the exact DISTINCTCOUNT / value-count pass.
 int32_t PlanBuilder::plan_group_table() {
+  // (a column named by two entries of columns[] -- a transformed group-by key owns its entry -- is one column of the
+  // reference's projection)
+  auto same_column_once = [&](std::vector<bool> &counted) {
+    for (int c = 1; c < nreal; c++)
+      for (int b = 0; b < c && counted[c]; b++)
+        if (counted[b] && strcmp(q->columns[b], q->columns[c]) == 0) counted[c] = false;
+  };
   {
     std::vector<bool> counted = projected;  // (tuple keys: the query's own group-by columns are the projected ones)
     if (P.tuple_keys)
@@ -3771,6 +3988,7 @@ int32_t PlanBuilder::plan_group_table() {
       counted[nreal + j] = false;
       for (int c : derived_inputs[j]) counted[c] = true;
     }
+    same_column_once(counted);
     for (bool p : counted) P.num_projected += p ? 1 : 0;
   }
   // ... and per filter program (several programs: each info's own projection): the distinct columns its functions
@@ -3784,6 +4002,7 @@ int32_t PlanBuilder::plan_group_table() {
       else
         for (int i : derived_inputs[c - nreal]) counted[i] = true;
     }
+    same_column_once(counted);
     for (bool b : counted) P.prog_projected[p] += b ? 1 : 0;
   }
 
@@ -3807,7 +4026,7 @@ int32_t PlanBuilder::plan_group_table() {
       if (P.tuple_keys) {
         r = P.tuple_remap;
       } else {
-        int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], r, null_key);
+        int32_t rc = build_remap(*P.dev, segp, ci, q->columns[c], r, null_key, key_transform(k));
         if (rc) return rc;
       }
       P.gb_dicts.push_back(r);
@@ -3910,7 +4129,7 @@ int32_t PlanBuilder::stage_segments() {
   // group-by records (build_records): dense key spaces of dictionary keys, for every group-by the aggregation kernel
   // walks (PHIP_GB_RECORD=0: the columns' own layouts; =1: a record for any number of fields, else from kRecMinFields)
   rec_want = P.group_by && P.dq.mode != GB_HASH && gb_key_space <= ((int64_t)1 << 22) && !P.want_bitmap &&
-             q->num_group_by <= kRecKeys && !env_off("PHIP_GB_RECORD");
+             q->num_group_by <= kRecKeys && !env_off("PHIP_GB_RECORD") && !gb_transformed;
   rec_min_fields = env_int("PHIP_GB_RECORD", 0) == 1 ? 1 : kRecMinFields;
   for (int a = 0; a < kMaxAggs; a++) P.dq.rec_fa[a] = P.dq.rec_fb[a] = -1;
   // PHIP_HLL_DOC (measurement override): "0" = gather the per-id table
@@ -7496,6 +7715,100 @@ PHIP_API int32_t phip_segment_match_dictionary(uint64_t handle, const char *colu
   return PHIP_OK;
 }
 
+static bool has_key_transform(const phip_query_desc *q) {
+  for (int k = 0; q->group_by_transforms && k < q->num_group_by; k++)
+    if (q->group_by_transforms[k].function != PHIP_TT_NONE) return true;
+  return false;
+}
+
+// WHERE f(col) <op> literal over a dictionary column: the program and the comparison over the dictionary's entries,
+// not the docs (transform.hip dict_transform_kernel's match form), the twin of phip_segment_match_dictionary.
+PHIP_API int32_t phip_segment_match_transform(uint64_t handle, const char *column, const phip_time_transform *transform,
+                                              const phip_transform_predicate *predicate, uint64_t *out_words,
+                                              int64_t num_words) {
+  if (!column || !transform || !predicate || !out_words || num_words < 0) return fail(PHIP_ERR_INVALID, "null argument");
+  TimeProgram prog;
+  int32_t rc = time_program(transform, &prog);
+  if (rc) return rc;
+  const phip_transform_predicate &pr = *predicate;
+  if (pr.kind != PHIP_TT_PRED_RANGE && pr.kind != PHIP_TT_PRED_SET)
+    return fail(PHIP_ERR_INVALID, "transform predicate: kind %d", pr.kind);
+  if ((pr.exclusive & ~1) || (pr.lower_inclusive & ~1) || (pr.upper_inclusive & ~1))
+    return fail(PHIP_ERR_INVALID, "transform predicate: a flag is neither 0 nor 1");
+  if (pr.kind == PHIP_TT_PRED_SET) {
+    if (pr.num_values < 0 || (pr.num_values > 0 && !pr.values))
+      return fail(PHIP_ERR_INVALID, "transform predicate: %d values at a null pointer", pr.num_values);
+    for (int32_t i = 1; i < pr.num_values; i++)
+      if (pr.values[i - 1] >= pr.values[i]) return fail(PHIP_ERR_INVALID, "transform predicate: values do not ascend at %d", i);
+  }
+  std::shared_ptr<Segment> seg;
+  Device *dev;
+  {
+    std::lock_guard<std::mutex> g(g_mu);
+    auto it = g_segments.find(handle);
+    if (it == g_segments.end()) return fail(PHIP_ERR_NOT_FOUND, "unknown segment handle");
+    seg = it->second;
+    dev = find_device(seg->device);
+  }
+  if (!dev) return fail(PHIP_ERR_NO_DEVICE, "device %d not initialised", seg->device);
+  auto ci = seg->by_name.find(column);
+  if (ci == seg->by_name.end()) return fail(PHIP_ERR_NOT_FOUND, "segment %s has no column %s", seg->name.c_str(), column);
+  const ColumnStore &cs = seg->cols[ci->second];
+  if ((rc = time_transform_column(cs, prog))) return rc;
+  const int64_t need = ((int64_t)cs.card + 63) / 64;
+  if (num_words < need) return fail(PHIP_ERR_INVALID, "column %s: %lld words for %d dictionary entries", column, (long long)num_words, cs.card);
+  if (!g_transform)
+    return fail(PHIP_ERR_UNSUPPORTED, "a time transform over column %s: this library was built without the transform "
+                "kernels", column);
+  memset(out_words, 0, (size_t)num_words * 8);
+  if (cs.card == 0) return PHIP_OK;
+  std::lock_guard<std::mutex> dl(dev->mu);
+  HIP_TRY(hipSetDevice(dev->ordinal));
+  hipStream_t st = dev->stream;
+  const int32_t ntiles = (int32_t)(((int64_t)cs.card + kTileDocs - 1) / kTileDocs);
+  const size_t set_off = round_up((int64_t)sizeof(TransformTask), 16);
+  const size_t set_bytes = pr.kind == PHIP_TT_PRED_SET ? (size_t)pr.num_values * 8 : 0;
+  const size_t out_off = round_up((int64_t)(set_off + set_bytes), 16);
+  const size_t total = out_off + (size_t)ntiles * 32 * 8;
+  void *tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, total));
+  struct Free {
+    void *p;
+    ~Free() { (void)hipFree(p); }
+  } free_tmp{tmp};
+  TransformTask t;
+  fill_transform_task(t, cs, prog);
+  t.match = (uint64_t *)((uint8_t *)tmp + out_off);
+  t.pred = pr.kind == PHIP_TT_PRED_RANGE ? kTtPredRange : kTtPredSet;
+  t.invert = pr.exclusive;
+  if (pr.kind == PHIP_TT_PRED_RANGE) {
+    t.lo = pr.lower;
+    t.hi = pr.upper;
+    t.lo_inclusive = pr.lower_inclusive;
+    t.hi_inclusive = pr.upper_inclusive;
+  } else {
+    t.set = (const int64_t *)((uint8_t *)tmp + set_off);
+    t.set_count = pr.num_values;
+  }
+  std::vector<uint8_t> stage(out_off, 0);
+  memcpy(stage.data(), &t, sizeof(t));
+  if (set_bytes) memcpy(stage.data() + set_off, pr.values, set_bytes);
+  HIP_TRY(hipMemcpyAsync(tmp, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+  hipError_t e = g_transform->dict((const TransformTask *)tmp, cs.card, transform_grid_blocks(*dev), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_words, t.match, (size_t)need * 8, hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);  // (the staging vector and tmp outlive the copies)
+  HIP_TRY(e);
+  HIP_TRY(e2);
+  g_transform_match_launches++;
+  return PHIP_OK;
+}
+
+PHIP_API int32_t phip_transform_info(int64_t *out_remap_builds, int64_t *out_match_launches) {
+  if (out_remap_builds) *out_remap_builds = g_transform_remap_builds.load();
+  if (out_match_launches) *out_match_launches = g_transform_match_launches.load();
+  return PHIP_OK;
+}
+
 PHIP_API int32_t phip_segment_derived_info(uint64_t handle, int32_t *out_count, int64_t *out_bytes, int64_t *out_builds) {
   std::shared_ptr<Segment> seg;
   Device *dev;
@@ -7520,6 +7833,7 @@ PHIP_API int32_t phip_query(const phip_query_desc *query, phip_result **out_resu
   if (!out_result) return fail(PHIP_ERR_INVALID, "null result pointer");
   *out_result = nullptr;
   if (query && node_wanted(query)) {  // segments on several devices: a node plan, run once
+    if (has_key_transform(query)) return fail(PHIP_ERR_UNSUPPORTED, "a time transform of a group-by key in a node plan");
     uint64_t h = 0;
     int32_t rc = node_create(query, &h);
     if (rc) return rc;
@@ -7538,7 +7852,10 @@ static int32_t create_single_plan(const phip_query_desc *query, uint64_t *out_pl
 PHIP_API int32_t phip_plan_create(const phip_query_desc *query, uint64_t *out_plan) {
   if (!out_plan) return fail(PHIP_ERR_INVALID, "null plan pointer");
   *out_plan = 0;
-  if (query && node_wanted(query)) return node_create(query, out_plan);
+  if (query && node_wanted(query)) {
+    if (has_key_transform(query)) return fail(PHIP_ERR_UNSUPPORTED, "a time transform of a group-by key in a node plan");
+    return node_create(query, out_plan);
+  }
   return create_single_plan(query, out_plan);
 }
 

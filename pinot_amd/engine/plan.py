@@ -27,6 +27,7 @@ import numpy as np
 from .. import _lib
 from ..query import predicate as predeval
 from ..query import regex_dfa
+from ..query import time_transform
 from ..query.context import (MV_AGGREGATIONS, REFUSED_MV_AGGREGATIONS, UNBOUNDED, AggregationInfo, FilterClause,
                              FilterContext, Function, Identifier, Literal, Predicate, QueryContext, columns_of, sv_twin)
 from ..query.sql import parse
@@ -213,9 +214,42 @@ def _match_predicate(seg: GpuSegment, pred):
     return _Leaf(_lib.LEAF_DICT_SET, column, ids=np.asarray(ids, dtype=np.int32), pattern=True)
 
 
+def predicate_transform(pred):
+    """The compiled time transform on a predicate's left-hand side, or None (a column, or an expression that keeps
+    its present refusal)."""
+    return time_transform.compile_transform(pred.lhs) if isinstance(pred.lhs, Function) else None
+
+
+def _transform_predicate(seg: GpuSegment, pred, tt):
+    """f(col) <op> literal with f a time transform over a dictionary column: like a pattern (_match_predicate), f and
+    the comparison run over the dictionary's entries, not the docs (GpuSegment.match_transform), and the matching ids
+    feed a forward-index scan leaf -- DICT_RANGE when they are contiguous (a monotone f's range always is), else
+    DICT_SET, an empty set included -- whatever index the column has and never a constant: the reference's
+    ExpressionFilterOperator always scans and counts one entry per doc it evaluates
+    (ExpressionScanDocIdIterator.java:151)."""
+    column = tt.column
+    if pred.type in ("IS_NULL", "IS_NOT_NULL", "REGEXP_LIKE"):
+        raise UnsupportedOnGpu(f"{pred.type} over the time transform {pred.lhs} is not on the GPU path")
+    if not seg.has_column(column):
+        raise KeyError(f"segment {seg.name} has no column {column}")
+    m = seg.column_metadata(column)
+    time_transform.check_column(tt, m, seg.name)
+    if m.cardinality:
+        d = seg.dictionary(column).values
+        time_transform.check_range(tt, int(d[0]), int(d[-1]))
+    kind, lo, hi, members = time_transform.integer_predicate(pred, column)
+    ids = seg.match_transform(column, tt.program, (kind, lo, hi, tuple(int(v) for v in members)))
+    if len(ids) and int(ids[-1]) - int(ids[0]) + 1 == len(ids):
+        return _Leaf(_lib.LEAF_DICT_RANGE, column, lo=int(ids[0]), hi=int(ids[-1]) + 1, pattern=True)
+    return _Leaf(_lib.LEAF_DICT_SET, column, ids=np.asarray(ids, dtype=np.int32), pattern=True)
+
+
 def compile_predicate(seg: GpuSegment, pred) -> object:
     if pred.type == "REGEXP_LIKE":
         return _match_predicate(seg, pred)
+    tt = predicate_transform(pred)
+    if tt is not None:
+        return _transform_predicate(seg, pred, tt)
     column = pred.column
     if pred.type in ("IS_NULL", "IS_NOT_NULL"):
         return _null_leaf(seg, column, pred.type == "IS_NOT_NULL")
@@ -297,6 +331,13 @@ def _three_valued(seg: GpuSegment, fc: FilterContext):
     if fc.type == "PREDICATE":
         pred = fc.predicate
         p = compile_predicate(seg, pred)
+        tt = predicate_transform(pred) if pred.type != "REGEXP_LIKE" else None
+        if tt is not None:
+            # (the reference evaluates the transform over the null docs' default values and then masks them: not here)
+            if seg.has_null_vector(tt.column):
+                raise UnsupportedOnGpu(f"enableNullHandling: the time transform {pred.lhs} in a filter over column "
+                                       f"{tt.column}, which has a null vector in segment {seg.name}")
+            return p, _fold_not(p), None
         if pred.type in ("IS_NULL", "IS_NOT_NULL") or not seg.has_null_vector(pred.column):
             return p, _fold_not(p), None
         n, nn = _null_leaf(seg, pred.column), _null_leaf(seg, pred.column, True)
@@ -692,9 +733,16 @@ class GpuCombineOperator:
         self.query = query
         self.segments = list(segments)
         self.num_groups_limit = num_groups_limit
+        # group-by keys: columns, or time transforms of one dictionary column (query.time_transform): per key None or
+        # the compiled transform. Any other expression stays with the CPU plan maker.
+        self.key_transforms = []
         for e in query.group_by:
+            tt = None
             if not isinstance(e, Identifier):
-                raise UnsupportedOnGpu(f"group-by expression {e}")
+                tt = time_transform.compile_transform(e)
+                if tt is None:
+                    raise UnsupportedOnGpu(f"group-by expression {e}")
+            self.key_transforms.append(tt)
         check_multi_value(query, self.segments, segment_filters is not None)
         self.num_programs = len(programs[0]) if programs is not None else 1
         self.stats_programs = 0  # phip_query_desc.stats_programs: 0 = every program's scans count
@@ -765,16 +813,47 @@ class GpuCombineOperator:
             for c in (p[2], p[3]):
                 if c is not None and c not in cols:
                     cols.append(c)
-        for e in query.group_by:
-            if e.name not in cols:
-                cols.append(e.name)
+        # key k reads entry key_slots[k] of the descriptor's columns. A transformed key gets an entry of its own, after
+        # the others (the column named once more): an entry carries one remap (phip_query_desc.group_by_transforms).
+        self.key_slots = [None] * len(query.group_by)
+        for k, (e, tt) in enumerate(zip(query.group_by, self.key_transforms)):
+            if tt is None:
+                if e.name not in cols:
+                    cols.append(e.name)
+                self.key_slots[k] = cols.index(e.name)
+        for k, tt in enumerate(self.key_transforms):
+            if tt is not None:
+                self.key_slots[k] = len(cols)
+                cols.append(tt.column)
         self.columns = cols
         for s in self.segments:
             for c in cols:
                 if not s.has_column(c):
                     raise KeyError(f"segment {s.name} has no column {c}")
+        self._check_key_transforms(segment_filters is not None, nh)
         self._check_derived(segment_filters is not None)
         self._refuse_nan_extrema()
+
+    def _check_key_transforms(self, star_tree, null_handling):
+        """What a transformed group-by key may read: one single-value dictionary INT / LONG column of segments on one
+        device, without nulls to key under null handling, whose values the program cannot overflow on."""
+        for e, tt in zip(self.query.group_by, self.key_transforms):
+            if tt is None:
+                continue
+            if star_tree:
+                raise UnsupportedOnGpu(f"the time transform {e} as a group-by key over a star-tree's documents")
+            if len({s.device for s in self.segments}) > 1:
+                raise UnsupportedOnGpu(f"the time transform {e} as a group-by key over segments on several devices "
+                                       f"(a node plan)")
+            for s in self.segments:
+                m = s.column_metadata(tt.column)
+                time_transform.check_column(tt, m, s.name)
+                if null_handling and s.has_null_vector(tt.column):
+                    raise UnsupportedOnGpu(f"enableNullHandling: the time transform {e} as a group-by key over column "
+                                           f"{tt.column}, which has a null vector in segment {s.name}")
+                if m.cardinality:
+                    d = s.dictionary(tt.column).values
+                    time_transform.check_range(tt, int(d[0]), int(d[-1]))
 
     def _check_derived(self, star_tree):
         """What a derived value column's program may read: numeric columns of the segments' own documents."""
@@ -868,7 +947,9 @@ class GpuCombineOperator:
                                                f"infinity in segment {s.name}: its values can be NaN")
 
     def _desc(self, keep):
-        col_index = {c: i for i, c in enumerate(self.columns)}
+        col_index = {}
+        for i, c in enumerate(self.columns):  # (a transformed key's own entry names its column again: the first one)
+            col_index.setdefault(c, i)
         q = _lib.QueryDesc()
         names = (ctypes.c_char_p * max(len(self.columns), 1))(*[c.encode() for c in self.columns])
         keep.append(names)
@@ -925,8 +1006,16 @@ class GpuCombineOperator:
             keep.append(dcols)
             q.num_derived = len(self.derived)
             q.derived = dcols
-        gb = (ctypes.c_int32 * max(len(self.query.group_by), 1))(*[col_index[e.name] for e in self.query.group_by])
+        gb = (ctypes.c_int32 * max(len(self.query.group_by), 1))(*self.key_slots)
         keep.append(gb)
+        if any(tt is not None for tt in self.key_transforms):
+            tts = (_lib.TimeTransform * len(self.key_transforms))()
+            for k, tt in enumerate(self.key_transforms):
+                if tt is not None:
+                    (tts[k].function, tts[k].unit, tts[k].in_mul, tts[k].in_div, tts[k].out_mul,
+                     tts[k].out_div) = tt.program
+            keep.append(tts)
+            q.group_by_transforms = tts
         q.num_group_by = len(self.query.group_by)
         q.group_by_columns = gb
         q.num_groups_limit = self.num_groups_limit
@@ -1260,8 +1349,10 @@ class GpuCombineOperator:
 
     def key_types(self):
         """Stored types of the group-by columns, from the column metadata (the group-by block's DataSchema)."""
-        return [_STORED[self.segments[0].column_metadata(e.name).data_type] for e in self.query.group_by] \
-            if self.segments else None
+        if not self.segments:
+            return None
+        return [_STORED[self.segments[0].column_metadata(e.name).data_type] if tt is None else _STORED[tt.result_type]
+                for e, tt in zip(self.query.group_by, self.key_transforms)]
 
     def _block_from_result(self, res):
         lib = getattr(self, "_lib", None) or _lib.load()
@@ -2323,8 +2414,8 @@ class GpuGroupByCombineOperator:
         self.key_space = []
         for seg in self.segments:
             ks = 1
-            for e in query.group_by:
-                m = seg.column_metadata(e.name)
+            for e in query.group_by:  # (a time transform of a column has at most the column's values)
+                m = seg.column_metadata(e.name if isinstance(e, Identifier) else time_transform.compile_transform(e).column)
                 ks *= m.cardinality if m.has_dictionary else max(seg.num_docs, 1)
             self.key_space.append(ks)
         self.per_segment = None
@@ -2551,6 +2642,26 @@ def _query_columns(query: QueryContext):
     for e, _ in query.select:
         cols.update(c for c in columns_of(e) if c != "*")
     return cols
+
+
+def _has_time_transform(query: QueryContext) -> bool:
+    def in_filter(fc):
+        if fc is None:
+            return False
+        if fc.type == "PREDICATE":
+            return time_transform.transforms_in(fc.predicate.lhs)
+        return any(in_filter(c) for c in fc.children)
+
+    def in_expr(e):
+        if isinstance(e, FilterClause):
+            return in_expr(e.function) or in_filter(e.filter)
+        if isinstance(e, FilterContext):
+            return in_filter(e)
+        return time_transform.transforms_in(e) or (isinstance(e, Function) and any(in_expr(a) for a in e.args))
+
+    return (in_filter(query.filter) or any(in_expr(e) for e in query.group_by)
+            or any(in_expr(e) for e, _ in query.select)
+            or any(ag.argument is not None and in_expr(ag.argument) or in_filter(ag.filter) for ag in query.aggregations))
 
 
 def _has_nulls(query: QueryContext, segments) -> bool:
@@ -2924,7 +3035,9 @@ class GpuInstancePlanMaker:
             op = _null_handling_operator(query, segments, limit)
             if op is not None:
                 return op
-        st = GpuStarTreeOperator.plan(query, segments, limit) if not _has_nulls(query, segments) else None
+        # (a query with a time transform anywhere is not fitted to a star-tree)
+        st = GpuStarTreeOperator.plan(query, segments, limit) \
+            if not _has_nulls(query, segments) and not _has_time_transform(query) else None
         if st is not None:
             st.inner.device_trim = self.device_trim
             return st

@@ -20,6 +20,12 @@ from ..spi import DataType
 # device, a huge value = always the host. Measured crossover: DESIGN.md §3 "String matching".
 STRMATCH_HOST_CARD = 256
 
+# The same choice for a time transform's comparison over a numeric dictionary (match_transform): below this cardinality
+# query.time_transform.evaluate on the host, the others on the device (phip_segment_match_transform).
+# PINOT_AMD_TRANSFORM_HOST_CARD overrides it, as above. The default is the string match's: the crossover of this pair is
+# unmeasured (DESIGN.md §3 "Time transforms").
+TRANSFORM_HOST_CARD = 256
+
 
 class GpuSegment:
     def __init__(self, segment: ImmutableSegment, device: int = -1):
@@ -34,6 +40,8 @@ class GpuSegment:
         self._specials = {}  # column -> (holds NaN, holds an infinity): real_specials
         self._intervals = {}  # column -> (min, max) or None: value_interval
         self._matches = {}  # (column, pattern) -> matching dict ids: match_dictionary
+        self._transform_matches = {}  # (column, program, predicate) -> matching dict ids: match_transform
+        self.transform_match_builds = 0  # id sets match_transform computed (not found kept)
         cols = list(segment.columns.values())
         descs = (_lib.ColumnDesc * max(len(cols), 1))()
         keep = []
@@ -170,6 +178,45 @@ class GpuSegment:
             ids = np.flatnonzero(hit).astype(np.int32)
             if len(self._matches) < 1024:
                 self._matches[key] = ids
+        return ids
+
+    def match_transform(self, column, program, predicate) -> np.ndarray:
+        """Sorted int32 dict ids of the dictionary INT / LONG column's entries v whose time transform
+        (query.time_transform.Program ``program``) passes ``predicate`` = (kind, lo, hi, members) as
+        time_transform.integer_predicate resolves it -- what the reference's ExpressionFilterOperator finds out per
+        scanned doc, once per entry. Kept per (column, program, predicate)."""
+        from ..query import time_transform as tt
+        program = tt.Program(*program)
+        kind, lo, hi, members = predicate
+        key = (column, program, (kind, int(lo), int(hi), tuple(members)))
+        ids = self._transform_matches.get(key)
+        if ids is None:
+            self.transform_match_builds += 1
+            card = self.column_metadata(column).cardinality
+            host_card = int(os.environ.get("PINOT_AMD_TRANSFORM_HOST_CARD", TRANSFORM_HOST_CARD))
+            if card < host_card:
+                vals = tt.evaluate(program, np.asarray(self.dictionary(column).values, dtype=np.int64))
+                hit = tt.match_values(vals, kind, lo, hi, np.asarray(members, dtype=np.int64))
+            else:
+                t = _lib.TimeTransform(*program)
+                pr = _lib.TransformPredicate()
+                vals = np.ascontiguousarray(members, dtype=np.int64)
+                if kind == "range":
+                    pr.kind = _lib.TT_PRED_RANGE
+                    pr.lower, pr.upper, pr.lower_inclusive, pr.upper_inclusive = int(lo), int(hi), 1, 1
+                else:
+                    pr.kind = _lib.TT_PRED_SET
+                    pr.exclusive = int(kind == "not_set")
+                    pr.values = vals.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if len(vals) else None
+                    pr.num_values = len(vals)
+                words = np.zeros(max((card + 63) // 64, 1), dtype=np.uint64)
+                _lib.check(_lib.load().phip_segment_match_transform(
+                    self.handle, column.encode(), ctypes.byref(t), ctypes.byref(pr),
+                    words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(words)))
+                hit = np.unpackbits(words.view(np.uint8), bitorder="little")[:card].astype(bool)
+            ids = np.flatnonzero(hit).astype(np.int32)
+            if len(self._transform_matches) < 1024:
+                self._transform_matches[key] = ids
         return ids
 
     def derived_info(self):

@@ -134,6 +134,11 @@ class FilterContext:
 
     def columns(self) -> List[str]:
         if self.type == "PREDICATE":
+            lhs = self.predicate.lhs
+            if isinstance(lhs, Function):
+                from .time_transform import is_time_transform_name  # (imports this module)
+                if is_time_transform_name(lhs.name):  # a time transform of one column reads that column
+                    return columns_of(lhs)
             return [self.predicate.column]
         out = []
         for c in self.children:
